@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- numerical-factorization GFLOP/s of the MI355X path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full [--no-cpu]]
 
 A "step" is one numeric factorization (qr_factorize interval = the reference's "Factorize time",
 STMMQR/src/qr/SparseQR.c:346-355) of one matrix whose symbolic analysis is a committed fixture and whose values
@@ -14,7 +14,16 @@ already did; default mode "sharded": ONE matrix, subtrees on the ranks, contribu
 point-to-point messages, value = the matrix's flops / max-over-ranks time (strong scaling; the flop share of the
 critical path is printed).  `--mode replicas`: every rank its own matrix (weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed
+step) and the workload's `config`.  A plain run does only that: set-up, W warm-up steps, K timed steps, the line.
+
+--dump-outputs DIR: after the timed steps, the factors the last step left in HBM (what a caller of the timed path downloads)
+are written as DIR/<name>.npy, float64, at most 64 MB in all (fixed stratified samples of larger arrays; see dump_outputs).
+
+--full: everything else the benchmark measures, after the timed steps and outside `value`: the detail pass and the `roofline`
+object, Q'b and the least-squares solve on the resident factors (`f1_resident_factors`), the drop-in seam and the own symbolic
+phase, the large-front block of the default N = 1 workload, and the `cpu_baseline` object (the compiled reference, or the CPU
+restatement where it is not built; `--no-cpu` leaves it out).
 """
 import argparse
 import importlib
@@ -283,7 +292,7 @@ def micro_assembly_input(seed=99, P=8, FN=6144, FP=1024, CN=3000, NS=96):
 def run_micro(pkg, args):
     fronts = []
     orc = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from stmmqr_testlib import Oracle                # CPU baseline leg only
         orc = Oracle()
     for idx, (fm, fn, fp, dense) in enumerate([(a, b, c, d) for d in (False, True) for (a, b, c) in MICRO_FRONTS]):
@@ -415,6 +424,50 @@ def _install_guards(args, rank, world):
     return state
 
 
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: all files together
+DUMP_ARRAY_CAP = 1 << 19          # entries kept of any array but the packed R+H (4 MB each)
+DUMP_STACK_CAP = 1 << 22          # entries kept of the packed R+H (32 MB)
+
+
+def _stratified(a, k, seed):
+    """k entries of `a`, one from each of k equal strata at an offset drawn from a fixed seed: the same positions for the same
+    length in every run, spread over the whole array.  The whole array when it has at most k entries."""
+    if a.size <= k:
+        return a
+    edges = (np.arange(k + 1, dtype=np.int64) * a.size) // k
+    off = (np.random.default_rng(seed).random(k) * np.diff(edges)).astype(np.int64)
+    return a[edges[:-1] + off]
+
+
+def dump_outputs(ddir, plan, S):
+    """--dump-outputs: the factors the last timed step left in HBM, as a caller downloads them (the reference's qr_numeric:
+    packed R+H, HTau, the integer arrays, rank), written as DIR/<name>.npy in float64 (integers are exact there).  Arrays longer
+    than DUMP_ARRAY_CAP are fixed stratified samples; the packed R+H (1.2 GB on the default workload) is a sample of what room
+    is left under DUMP_LIMIT_BYTES, plus the sum of squares of every front's block of it (free of the row signs of R)."""
+    N = plan.download()
+    nf, rh = S.nf, int(N.rh_total)
+    stack = N.Stack[:rh]
+    order = np.asarray(S.Post[:nf], np.int64)                     # the blocks lie in the stack in postorder
+    starts = N.Rblock_off[order]
+    ends = np.append(starts[1:], rh)
+    front_sumsq = np.zeros(nf)
+    for f, a, b in zip(order, starts, ends):
+        front_sumsq[f] = np.dot(stack[a:b], stack[a:b])
+    arrays = {"info": np.array([N.rank, N.rank1, N.maxfrank, N.maxfm, rh]),
+              "HTau": N.HTau[:S.rjsize], "HStair": N.HStair[:S.rjsize], "Rdead": N.Rdead[:S.n], "HPinv": N.HPinv[:S.m],
+              "Hii": N.Hii[:S.hisize], "Hm": N.Hm[:nf], "Hr": N.Hr[:nf], "Rblock_off": N.Rblock_off[:nf],
+              "R_H_front_sumsq": front_sumsq}
+    out = {k: _stratified(np.asarray(v, np.float64), DUMP_ARRAY_CAP, seed) for seed, (k, v) in enumerate(arrays.items())}
+    used = sum(a.nbytes + 4096 for a in out.values()) + 4096      # (4 KB per file: the .npy header, generously)
+    out["R_H_stack_sample"] = _stratified(np.asarray(stack, np.float64), min(DUMP_STACK_CAP, (DUMP_LIMIT_BYTES - used) // 8), 99)
+    d = Path(ddir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, a in out.items():
+        np.save(d / f"{k}.npy", np.ascontiguousarray(a))
+    print(f"[bench] --dump-outputs: {len(out)} arrays, {sum(a.nbytes for a in out.values()) / 2**20:.1f} MB -> {d}",
+          file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -428,12 +481,16 @@ def main():
                     help="a Matrix Market file instead of a fixture: reader -> singletons + COLAMD + symbolic analysis of this library -> "
                          "timed numeric factorization; CPU leg = the compiled reference on the same file")
     ap.add_argument("--ordering", default="default", help="with --matrix: default | colamd (qrtest's third argument absent / 1)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the detail pass (roofline), the f1 block, the drop-in seam, the large-front block and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the factors of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--big-front-cols", type=int, default=None)
     ap.add_argument("--panel-algo", type=int, default=None)
     ap.add_argument("--lookahead", type=int, default=None)
     ap.add_argument("--no-large-front", dest="large_front", action="store_false",
-                    help="skip the un-headlined large-front block (c5mid / c5 stand-ins, ~15 s) of the default N = 1 line")
+                    help="with --full: skip the un-headlined large-front block (c5mid / c5 stand-ins, ~15 s) of the default N = 1 line")
     ap.add_argument("--tall-min", type=int, default=None)
     ap.add_argument("--fused-update", type=int, default=None)
     ap.add_argument("--use-graph", type=int, default=None)
@@ -445,6 +502,8 @@ def main():
                     help="sharded mode: 1 (default) = the heavy top fronts are SHARED by the ranks of their group (panels in turn, "
                          "every rank updates its own 32-column blocks: sharded.spread_partition); 0 = subtrees only")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.workload == "micro"):
+        ap.error("--dump-outputs: one process (--gpus 1) on a matrix workload only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
 
@@ -600,12 +659,14 @@ def _run(args, torch, rank, world, local, guard):
     # a step that silently ran twice (a bounded panel wait ran out and the factorization was repeated with one-workgroup
     # panels) is not a measurement
     assert retries == 0, f"{retries} factorization(s) of the timed region were repeated after a panel-wait timeout"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan, S)
 
     # One extra, un-timed factorization with an event pair around every launch of a category (panel / update / assembly /
     # pack), recorded on the plan's stream with NO synchronisation in between: the schedule runs exactly as in the timed
     # region, and the pairs give each kernel family's own time (kernel-only: what rocprofv3 --kernel-trace --stats sums).
     det, step_rows = None, []
-    if rank == 0:                      # (the detail pass feeds rank 0's roofline object only)
+    if rank == 0 and args.full:        # (the detail pass feeds rank 0's roofline object only)
         if sharded:
             plan.set_groups(np.zeros(S.nf, np.int32))
         # (STMMQR_DUMPSTEPS: the library writes one line per timeline step of a detail pass -- the tallest panel of the step and the
@@ -626,6 +687,8 @@ def _run(args, torch, rank, world, local, guard):
                 step_rows = []
     if rank == 0:
         value = total_flops * args.steps / wall * 1e-9
+    roof = None
+    if rank == 0 and args.full:
         # Algorithmic work: the reference's flop count (FLOP_COUNT, :1571) splits into the dlarfb flops handed to the
         # trailing update (4 * rows * cols * reflectors per panel: stats.flops_update) and the rest, which the panel kernels
         # do (dlarfg + in-panel dlarf + T).  Update bytes: 2 reads + 1 write of every trailing entry per panel = 24 B per
@@ -738,6 +801,7 @@ def _run(args, torch, rank, world, local, guard):
                             "peak": PEAK_HBM_GBS, "unit": "GB/s",
                             "frac": det["bytes_assemble"] / max(det["ms_assemble"], 1e-9) * 1e-6 / PEAK_HBM_GBS}
         roof["ms"] = {k: det[k] for k in ("ms_total", "ms_assemble", "ms_panel", "ms_small", "ms_update", "ms_pack")}
+    if rank == 0:
         oname = ORDERING_NAMES.get(int(g["ordering"][0]), str(int(g["ordering"][0]))) if "ordering" in g else "unknown"
         standin_of = {"xenon1": "xenon1.mtx", "sme3dc": "sme3Dc.mtx", "c5mid": "3D_51448_3D.mtx (structure only, n = 27 000)", "c5mini": "3D_51448_3D.mtx (structure only, n = 8000)",
                       "c5_": "3D_51448_3D.mtx (SURVEY 8d generator at full size, n = 52 022)"}
@@ -760,8 +824,8 @@ def _run(args, torch, rank, world, local, guard):
                                         if rehearsal else "")),
                        "flops_per_step": flops, "device_ms_per_step": dev_ms / args.steps, "launches_per_step": st["nlaunch"],
                        "levels": st["nlevels"], "timeline_steps": st["nsteps"], "retries": retries,
-                       "device_bytes": det.get("device_bytes", 0.0)},
-            "roofline": roof,
+                       "device_bytes": (det or st).get("device_bytes", 0.0)},
+            **({"roofline": roof} if roof is not None else {}),
         }
         if crit is not None:
             # model bound of the strong-scaling speed-up: whole tree's flop bound / flop bound on the critical path (per phase
@@ -781,7 +845,7 @@ def _run(args, torch, rank, world, local, guard):
         # SURVEY 8 (f1), outside the timed region: Q'b and the least-squares solve on the factors still resident in HBM
         # (wall time including the copies of the vectors), with the residual the reference's driver prints
         try:
-            if not sharded:
+            if args.full and not sharded:
                 from stmmqr_testlib import csc_matvec
                 Ap_, Ai_, Ax_ = g["in_Ap"], g["in_Ai"], g["in_Ax"]
                 xt = np.arange(S.n, dtype=np.float64)
@@ -807,7 +871,7 @@ def _run(args, torch, rank, world, local, guard):
         # factorization, D2H of the packed R+H, host allocation -- the interval the reference's "Factorize time" brackets
         # (SparseQR.c:346-377).  And the own symbolic phase: stmmqr_analyze on this matrix with its permutation.
         try:
-            if world == 1:
+            if args.full and world == 1:
                 # the exported qr_factorize itself (reference structs in, qr_numeric out), twice: the first call builds the plan,
                 # the second finds it in the seam's cache (same qr_symbolic, same pattern) -- what a refactorization costs
                 plan.close()                                        # (this process's bench plan: its HBM goes back first)
@@ -836,7 +900,7 @@ def _run(args, torch, rank, world, local, guard):
         # The large-front class (BASELINE configs[4]'s structure: one dense root front carries the flops, the quad update on the matrix
         # cores), un-headlined and outside `value`: the same library, the full-size stand-in and its n = 27 000 sibling, three / two
         # timed factorizations each after one warm-up, plus one detail pass for the update kernels' own share of the MFMA peak.
-        if world == 1 and args.large_front and name == DEFAULT_WORKLOAD.get(1) and mtx_path is None:
+        if args.full and world == 1 and args.large_front and name == DEFAULT_WORKLOAD.get(1) and mtx_path is None:
             lf = {}
             for wl_name, nsteps in (("c5mid_standin", 3), ("c5_standin", 2)):
                 try:
@@ -870,7 +934,7 @@ def _run(args, torch, rank, world, local, guard):
                 except Exception as e:      # noqa: BLE001 (the headline line must come out whatever happens here)
                     lf[wl_name] = {"error": str(e)[:300]}
             out["large_front"] = lf
-        if not args.no_cpu and world == 1:             # (the CPU baseline is reported at N = 1 only)
+        if args.full and not args.no_cpu and world == 1:     # (the CPU baseline is reported at N = 1 only)
             cb = cpu_baseline(name, g, mtx_path=mtx_path, flops=flops)
             if mtx_path is not None and cb.get("kind") == "reference":
                 fl_ref = [l for l in cb.get("legs", []) if l.get("mode", "").startswith("serial") and "value" in l]

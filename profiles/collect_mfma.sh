@@ -15,7 +15,7 @@ DIRS=""
 for C in SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE; do
   D=$OUT/${TAG}_pmc_$C
   rm -rf $D
-  if rocprofv3 --pmc $C --kernel-trace --output-format csv -d $D -o p -- python3 $ROOT/bench.py --workload $W --steps 1 --warmup 0 --no-cpu > $OUT/${TAG}_pmc_$C.log 2>&1; then
+  if rocprofv3 --pmc $C --kernel-trace --output-format csv -d $D -o p -- python3 $ROOT/bench.py --full --workload $W --steps 1 --warmup 0 --no-cpu > $OUT/${TAG}_pmc_$C.log 2>&1; then
     DIRS="$DIRS $D"; echo "$C ok"
   else
     echo "$C FAILED (see ${TAG}_pmc_$C.log)"; tail -3 $OUT/${TAG}_pmc_$C.log

@@ -63,3 +63,42 @@ def test_cpu_baseline_legs():
         assert ("value" in legs[2]) != ("error" in legs[2])
         for l in legs:
             assert ("FAILED" in cb["sample"]) == any("error" in x for x in legs)
+
+
+def test_dump_outputs_is_the_download_within_64_mb(tmp_path, oracle):
+    """--dump-outputs writes what plan.download() returns: float64 arrays that hold the integer arrays exactly, the whole packed
+    R+H of a small factorization, the sum of squares of every front's block; an R+H longer than the sample is cut to a fixed sample,
+    all files together stay within 64 MB, and the sample is the same in two runs."""
+    import types
+    import bench
+    from stmmqr_testlib import Symbolic, load_golden, scalar
+    g = load_golden("syn_grid3d")
+    S = Symbolic(g)
+    No = oracle.factorize(S, g["in_Ap"], g["in_Ai"], g["in_Ax"], scalar(g, "in_tol"), int(scalar(g, "in_ntol")))
+
+    class Plan:
+        def __init__(self, stack):
+            self.stack = stack
+
+        def download(self):
+            return types.SimpleNamespace(Stack=self.stack, Rblock_off=No.Rblock_off, Rdead=No.Rdead, HStair=No.HStair, HTau=No.HTau,
+                                         Hii=No.Hii, HPinv=No.HPinv, Hm=No.Hm, Hr=No.Hr, rank=No.c.rank, rank1=No.c.rank1,
+                                         maxfrank=No.c.maxfrank, maxfm=No.c.maxfm, rh_total=self.stack.size)
+
+    rh = No.c.rh_total
+    bench.dump_outputs(tmp_path / "a", Plan(No.Stack[:rh]), S)
+    out = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert all(a.dtype == np.float64 for a in out.values())
+    np.testing.assert_array_equal(out["R_H_stack_sample"], No.Stack[:rh])
+    np.testing.assert_array_equal(out["HStair"], No.HStair[:S.rjsize])
+    np.testing.assert_array_equal(out["Rdead"], No.Rdead[:S.n])
+    np.testing.assert_array_equal(out["info"], [No.c.rank, No.c.rank1, No.c.maxfrank, No.c.maxfm, rh])
+    blocks = No.rh_blocks(S)
+    np.testing.assert_allclose(out["R_H_front_sumsq"], [np.dot(blocks[f], blocks[f]) for f in range(S.nf)], rtol=1e-14)
+
+    big = np.random.default_rng(0).standard_normal(3 * bench.DUMP_STACK_CAP)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, Plan(big), S)
+        assert sum(f.stat().st_size for f in (tmp_path / d).glob("*.npy")) <= 64 << 20
+    b, c = np.load(tmp_path / "b" / "R_H_stack_sample.npy"), np.load(tmp_path / "c" / "R_H_stack_sample.npy")
+    assert b.size == bench.DUMP_STACK_CAP and np.array_equal(b, c) and np.all(np.isin(b[:100], big))

@@ -1,8 +1,8 @@
 """The driver's Matrix Market reader (stmmqr_read_matrix_market, csrc/stmmqr_mmio.cpp) against what the
 REFERENCE's reader (SparseCore_read_matrix, prefer = 1, as test/qrtest.c:112 calls it) makes of the same files.
 The expected arrays in tests/golden/mm/reference_reader.npz were dumped from the compiled reference (oracle/_ref/refdump);
-the two matrices of the reference's Data directory are compared with the A arrays of their golden fixtures when the
-checkout is present.  No GPU needed."""
+the two matrices of the reference's Data directory (stored under tests/golden/data) are compared with the A arrays of their
+golden fixtures.  No GPU needed."""
 import importlib
 from pathlib import Path
 
@@ -73,11 +73,12 @@ def test_reader_survives_hostile_headers(pkg, tmp_path):
 
 
 @pytest.mark.parametrize("name,fname", [("bcsstk14", "bcsstk14.mtx"), ("epb1", "epb1.mtx")])
-def test_reference_data_files(pkg, name, fname):
-    """bcsstk14.mtx is stored symmetric (lower triangle): the expansion must give the A the reference factorizes."""
-    path = Path("/root/reference/Data") / fname
-    if not path.exists():
-        pytest.skip("reference checkout not present")
+def test_reference_data_files(pkg, tmp_path, name, fname):
+    """bcsstk14.mtx is stored symmetric (lower triangle): the expansion must give the A the reference factorizes.
+    The files are the reference's Data/ files byte for byte, stored xz-compressed under tests/golden/data."""
+    import lzma
+    path = tmp_path / fname
+    path.write_bytes(lzma.decompress((ROOT / "tests" / "golden" / "data" / f"{fname}.xz").read_bytes()))
     from stmmqr_testlib import load_golden
     g = load_golden(name)
     m, n, Ap, Ai, Ax = pkg.read_matrix_market(path)
