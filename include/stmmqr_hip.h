@@ -291,7 +291,7 @@ int stmmqr_factorize_shared_front(stmmqr_plan *plan, int group, stm_long f, int 
  * stmmqr_factorize_phases: everything between stmmqr_factorize_begin and stmmqr_factorize_finish of a sharded factorization as ONE
  * call -- per phase k: the exchange (lists [out_ptr[k], out_ptr[k+1]) / [in_ptr[k], in_ptr[k+1])), then the shared front this rank
  * takes part in (shared_front[k] >= 0: panel loop + gather, group [shared_first[k], + shared_span[k])) or its own fronts of the
- * phase (has_group[k]: stmmqr_factorize_group(plan, k)).  The only host waits left are the four bytes stmmqr_factorize_group reads
+ * phase (has_group[k]: stmmqr_factorize_group(plan, k)).  The only host waits left are the eight bytes stmmqr_factorize_group reads
  * after a group. */
 int stmmqr_factorize_exchange(stmmqr_plan *plan, stm_long nout, const stm_long *out_front, const int *out_peer, stm_long nin,
                               const stm_long *in_front, const int *in_peer, const stmmqr_transport *tr);

@@ -108,7 +108,7 @@ __device__ __forceinline__ bool stm_wait_ge(const int *flag, int target, int *ab
 }
 
 // A bounded wait ran out: recorded on the front (which panel chain failed) AND in the plan-wide word abort[1], so that the host
-// learns it from four bytes instead of a copy of every FrontNum (stmmqr_factorize_group of the phased interface).
+// learns it from a few bytes instead of a copy of every FrontNum (stmmqr_factorize_group of the phased interface).
 // (abort is null in the single-front seams of stmmqr_seams.cpp: they read the front's own perr)
 #define STM_SET_PERR(c, num) do { st_agent(&(num)->perr, 1); if ((c).abort) st_agent((c).abort + 1, 1); } while (0)
 

@@ -13,6 +13,9 @@
 // gfx950 device is usable the entry points fail with STMMQR_ERR_DEVICE.
 #include "stmmqr_plan.h"
 
+#include <functional>
+#include <string>
+
 thread_local std::string g_err;
 stmmqr_options g_opt = {STM_NB, 64, 0, 0, 0, 1, STM_TALL_MIN, 2, 0, 4};      // (panel_algo 0: by panel height; lookahead 2: passenger launches)
 size_t g_chunk[4] = {32, 5000, 4, 4};     // FCHUNK, SMALL, MINCHUNK, MINCHUNK_RATIO (SparseQR.h:16-19)
@@ -626,9 +629,8 @@ void build_schedule(stmmqr_plan &P, std::vector<int> &tslot)
             //  larger than the full-rank pattern says; an arena that overflows is regrown to the hard bound and the factorization
             //  repeated once -- stats.retries says so)
             if (!P.rh_grow && P.rh_est_total > 0) {
-                // (STMMQR_RH_EST_SCALE: tests shrink the estimate to drive the overflow path)
-                const double sc = getenv("STMMQR_RH_EST_SCALE") ? atof(getenv("STMMQR_RH_EST_SCALE")) : 1.0;
-                const long long est = (long long)((double)P.rh_est_total * sc);
+                // (P.rh_est_scale: tests shrink the estimate to drive the overflow path)
+                const long long est = (long long)((double)P.rh_est_total * P.rh_est_scale);
                 P.rh_cap = std::max(1LL, std::min(P.rh_cap, est + est / 8 + 4096));
             }
             const auto pk = timeline_offsets(P, P.kept, nstep, true);
@@ -707,6 +709,8 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
     P.m = v.m; P.n = v.n; P.anz = v.anz; P.nf = v.nf; P.maxfn = v.maxfn; P.rjsize = v.rjsize;
     P.hisize = v.hisize; P.do_rank = v.do_rank_detection ? 1 : 0;
     P.maxstack = v.maxstack > 0 ? v.maxstack : 0;
+    // (a plan-time knob that every later rebuild of the schedule keeps: a reschedule must not give the plan another arena)
+    P.rh_est_scale = getenv("STMMQR_RH_EST_SCALE") ? atof(getenv("STMMQR_RH_EST_SCALE")) : 1.0;
     const long m = v.m, n = v.n, nf = v.nf;
     if (m < 0 || n < 0 || nf < 0) return fail(STMMQR_ERR_INVALID, "negative dimension");
     if (v.anz >= (1L << 31) - 1 || v.rjsize >= (1L << 31) - 1 || v.hisize >= (1L << 31) - 1 || m >= (1L << 30) ||
@@ -973,7 +977,11 @@ int reset_group(stmmqr_plan &P, int grp)
     HIPCHK(hipMemsetAsync(P.d_wcnt2.p, 0, P.wcnt_n * sizeof(int), st));
     HIPCHK(hipMemsetAsync(P.d_wflag.p, 0, P.wcnt_n * sizeof(int), st));
     HIPCHK(hipMemsetAsync(P.d_wflag2.p, 0, P.wcnt_n * sizeof(int), st));
-    HIPCHK(hipMemsetAsync(P.d_abort.p, 0, 3 * sizeof(int), st));   // ([3], a refused message of the subtree exchange, stays)
+    // abort[0..1] only: [3], a refused message of the subtree exchange, stays, and [2] goes back to what the groups before this one
+    // left (P.abort2_before: a front of an EARLIER group that outlived its cut schedule must still be reported at finish, while a
+    // front of this group that the wait left unfinished is not such a front -- the rerun raises [2] again if it is one)
+    HIPCHK(hipMemsetAsync(P.d_abort.p, 0, 2 * sizeof(int), st));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(P.d_abort.p + 2), P.abort2_before, 1, st));
     // slab recycling: a recycling plan holds the whole tree in this one group, and the aborted attempt has staged packed blocks behind
     // the arena's bump pointer; the rerun stages every block again, so the pointer (and the overflow word) go back to zero -- otherwise
     // the second set lands behind the first and overflows an arena that holds the estimate + 12.5 %
@@ -1392,8 +1400,11 @@ int run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req = null
     return 0;
 }
 
-int run_pack(stmmqr_plan &P)
+// overflow: the slab recycling's arena did not hold every packed block (k_cpack staged nothing past it); the caller decides what
+// that means (stmmqr_factorize_finish: a schedule or wait failure explains it, otherwise the arena grows)
+int run_pack(stmmqr_plan &P, bool &overflow)
 {
+    overflow = false;
     hipStream_t st = P.stream;
     const DevCtx c = P.ctx();
     const int *L0 = P.d_lists.p;
@@ -1417,12 +1428,7 @@ int run_pack(stmmqr_plan &P)
         HIPCHK(hipStreamSynchronize(st));
         P.rh_total = total;
         P.stats.nlaunch += 2;
-        if (top[1] != 0) {
-            if (!P.rh_grow) P.rh_grow = 1;                            // next: the hard bound (QRsym->maxstack / all recycled slabs)
-            else P.overflowed = true;                                 // that too: no recycling for this plan
-            P.arena_overflow = true;
-            return fail(STMMQR_ERR_OUT_OF_MEMORY, "the packed factors exceed the R+H arena of the slab recycling");
-        }
+        overflow = (top[1] != 0);
         return 0;
     }
     LCHK(stm_launch_rh_count(c, L0 + P.own_off, P.n_own, st));
@@ -1442,6 +1448,16 @@ int run_pack(stmmqr_plan &P)
 // (what the other host translation units need of the planner / scheduler: stmmqr_plan.h)
 int stm_run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req) { return run_schedule(P, detail, grp, req); }
 int stm_ensure_device(int device) { return ensure_device(device); }
+
+// The schedule rebuilt on the plan's own grouping (after a factorization that asked for another schedule: the full one, a larger
+// arena, the cut one on or off).  P.group holds the group ids only; the shared fronts get their STMMQR_GROUP_SHARED bit back, or
+// stmmqr_plan_set_groups would take them for fronts of this rank alone.
+static int regroup_same(stmmqr_plan &P)
+{
+    std::vector<int> grp(P.group.begin(), P.group.end());
+    for (size_t f = 0; f < grp.size(); f++) if (f < P.shared.size() && P.shared[f]) grp[f] |= STMMQR_GROUP_SHARED;
+    return stmmqr_plan_set_groups(&P, grp.data());
+}
 
 // =================================================================================================
 // C ABI
@@ -1581,8 +1597,7 @@ int stmmqr_factorize_begin(stmmqr_plan *plan, const stm_long *Ap, const stm_long
         P.early_end_failed = false;
         P.full_schedule = true;
         P.begun = false;
-        std::vector<int> grp(P.group.begin(), P.group.end());
-        int e = stmmqr_plan_set_groups(plan, grp.data());
+        int e = regroup_same(P);
         if (e) return e;
     }
     if (P.arena_overflow && P.recycle && !P.whole_call) {
@@ -1592,9 +1607,7 @@ int stmmqr_factorize_begin(stmmqr_plan *plan, const stm_long *Ap, const stm_long
         // caller that simply tries again gets the arena at its hard bound (then no recycling) instead of the same failure.
         P.arena_overflow = false;
         P.begun = false;
-        std::vector<int> grp(P.group.begin(), P.group.end());
-        for (size_t f = 0; f < grp.size(); f++) if (f < P.shared.size() && P.shared[f]) grp[f] |= STMMQR_GROUP_SHARED;
-        int e = stmmqr_plan_set_groups(plan, grp.data());
+        int e = regroup_same(P);
         if (e) return e;
     }
     const double host_ms_plan = P.stats.ms_host;
@@ -1607,6 +1620,7 @@ int stmmqr_factorize_begin(stmmqr_plan *plan, const stm_long *Ap, const stm_long
     P.evused = 0;
     P.begun = true;
     P.first_group = true;
+    P.abort2_before = 0;                                       // (reset_factorization clears abort[])
     if (!P.do_rank) tol = -1;                                  // SparseQR_factorize.c:285-289
     P.last_tol = tol; P.last_ntol = ntol;
     hipStream_t st = P.stream;
@@ -1625,6 +1639,7 @@ int stmmqr_factorize_group(stmmqr_plan *plan, int group, int detail)
     stmmqr_plan &P = *plan;
     HIPCHK(hipSetDevice(P.device));
     int e = 0;
+    const bool recoverable = !P.whole_call && !P.serial_panels;
     const bool graph_ok = g_opt.use_graph && !detail && group == 0 && P.first_group && !getenv("STMMQR_DUMPLV");
     if (graph_ok) {
         // replay the step schedule of group 0 as a hipGraph, captured once per plan and per everything that travels in the
@@ -1632,13 +1647,16 @@ int stmmqr_factorize_group(stmmqr_plan *plan, int group, int detail)
         // rebuilds the lists and may move the workspaces) and the run-time options
         const DevCtx c = P.ctx();
         // (everything run_schedule reads at capture time and that decides WHAT is launched or travels in the kernel arguments: the
-        //  run-time options incl. pair_update, STMMQR_TUNE, and the look-ahead thresholds of the environment)
+        //  run-time options incl. pair_update, STMMQR_TUNE, the look-ahead thresholds and the passenger knobs of the environment;
+        //  STMMQR_PASS_K is a real number: its text is the key)
         auto envl = [](const char *k, long dflt) { return getenv(k) ? atol(getenv(k)) : dflt; };
         long long optkey = 1469598103934665603LL;
         for (long long v : {(long long)g_opt.lookahead, (long long)g_opt.split_update, (long long)g_opt.fused_update, (long long)g_opt.pair_update,
                             (long long)P.serial_panels, (long long)c.tune, (long long)envl("STMMQR_LA_MIN", 2500), (long long)envl("STMMQR_LA_MIN_FUSED", 1500),
                             (long long)envl("STMMQR_LA_FUSED_ROWS", 5120), (long long)envl("STMMQR_LA_MAXPWG", 48), (long long)envl("STMMQR_LA_SYSFENCE", 0),
-                            (long long)envl("STMMQR_SIDE_RESERVE", 32)})
+                            (long long)envl("STMMQR_SIDE_RESERVE", 32), (long long)envl("STMMQR_PASSENGERS", 1), (long long)envl("STMMQR_PASS_ROWS", 16384),
+                            (long long)envl("STMMQR_PASS_MAXWG", 384), (long long)envl("STMMQR_PASS_TILES", 1L << 40), (long long)envl("STMMQR_CA_RIDERS", 1),
+                            (long long)envl("STMMQR_PASS_ABL", 0), (long long)std::hash<std::string>()(getenv("STMMQR_PASS_K") ? getenv("STMMQR_PASS_K") : "")})
             optkey = (optkey ^ v) * 1099511628211LL;
         if (!P.graph_exec || P.graph_tol != c.tol || P.graph_ntol != c.ntol || P.graph_dbg != c.dbg || P.graph_gen != P.sched_gen ||
             P.graph_opt != optkey) {
@@ -1682,11 +1700,14 @@ int stmmqr_factorize_group(stmmqr_plan *plan, int group, int detail)
     // Phased use (begin / group / finish called by the host: the sharded path): a bounded panel wait that ran out is found
     // HERE and the group is run again with one-workgroup panels (no inter-workgroup waits), exactly as
     // stmmqr_factorize_device does for the whole factorization -- the other groups and the imported fronts are not touched.
-    if (!e && !P.whole_call && !P.serial_panels) {
-        // (four bytes: the kernels raise abort[1] beside the front's own perr -- not a copy of every FrontNum per phase)
-        int failed = 0;
-        HIPCHK(hipMemcpyAsync(&failed, P.d_abort.p + 1, sizeof(int), hipMemcpyDeviceToHost, P.stream));
+    if (!e && recoverable) {
+        // (eight bytes: the kernels raise abort[1] beside the front's own perr -- not a copy of every FrontNum per phase -- and
+        //  abort[2], which the host keeps as it stands after every group that needs no rerun)
+        int flags[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(flags, P.d_abort.p + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, P.stream));
         HIPCHK(hipStreamSynchronize(P.stream));
+        const int failed = flags[0];
+        if (!failed) P.abort2_before = flags[1];
         if (failed) {
             if (g_opt.verbose) fprintf(stderr, "[stmmqr_hip] a panel wait ran out in group %d: running it again with one-workgroup panels\n", group);
             P.stats.retries++;
@@ -1694,6 +1715,10 @@ int stmmqr_factorize_group(stmmqr_plan *plan, int group, int detail)
             P.serial_panels = true;
             if (!e) e = run_schedule(P, detail != 0, group);
             P.serial_panels = false;
+            if (!e) {
+                HIPCHK(hipMemcpyAsync(&P.abort2_before, P.d_abort.p + 2, sizeof(int), hipMemcpyDeviceToHost, P.stream));
+                HIPCHK(hipStreamSynchronize(P.stream));
+            }
         }
     }
     P.first_group = false;
@@ -1707,18 +1732,48 @@ int stmmqr_factorize_finish(stmmqr_plan *plan, stmmqr_stats *stats)
     HIPCHK(hipSetDevice(P.device));
     hipStream_t st = P.stream;
     HIPCHK(hipEventRecord(P.ev[4], st));
-    int e = run_pack(P);
+    bool overflow = false;
+    int e = run_pack(P, overflow);
     if (e) return e;
     HIPCHK(hipEventRecord(P.ev[5], st));
-    int hard[2] = {0, 0};                                     // abort[2]: a front outlived its schedule; abort[3]: a refused message
-    HIPCHK(hipMemcpyAsync(hard, P.d_abort.p + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    int hard[3] = {0, 0, 0};                                  // abort[1]: a bounded wait ran out; [2]: a front outlived its schedule; [3]: a refused message
+    HIPCHK(hipMemcpyAsync(hard, P.d_abort.p + 1, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (hard[1]) return fail(STMMQR_ERR_DEVICE, "a contribution block received from another rank does not fit its front's symbolic bounds");
-    if (hard[0]) {
+    // per-front numeric summary (small): flops, ranks, and which panel chain gave up waiting
+    P.h_fnum.resize((size_t)std::max(1L, P.nf));
+    if (P.nf > 0)
+        HIPCHK(hipMemcpy(P.h_fnum.data(), P.d_fnum.p, (size_t)P.nf * sizeof(FrontNum), hipMemcpyDeviceToHost));
+    bool perr = hard[0] != 0;
+    for (long f = 0; f < P.nf; f++) {
+        if (P.group[f] < 0) continue;                  // factorized elsewhere
+        const FrontNum &nm = P.h_fnum[f];
+        const FrontSym &s = P.fs[f];
+        perr = perr || nm.perr;
+        if (getenv("STMMQR_DBG_EARLY") && s.nsched < s.npanels && (!nm.done || nm.g < std::min(nm.fm, s.fn)))
+            fprintf(stderr, "[early] front %ld fn %d fp %d fm %d fm_est %d fm_ub %d g %d rank %d done %d nsched %d npanels %d\n", f, s.fn, s.fp, nm.fm, s.fm_est,
+                    s.fm_ub, nm.g, nm.rank, nm.done, s.nsched, s.npanels);
+    }
+    // The causes, most specific first.  A wait that ran out leaves its front unfinished, so it also looks like a front that outlived
+    // its schedule: that is the wait's failure (serial retry, the cut schedule stays).  Either leaves fronts that packed what they
+    // held when they stopped, which may not fit the recycled arena: that overflow is theirs, not the arena's (rh_grow stays).
+    if (hard[2]) return fail(STMMQR_ERR_DEVICE, "a contribution block received from another rank does not fit its front's symbolic bounds");
+    if (perr) {
+        P.panel_wait_failed = true;
+        P.evused = 0;
+        return fail(STMMQR_ERR_DEVICE, "a panel workgroup gave up waiting for its neighbours (device shared with another job?)");
+    }
+    if (hard[1]) {
         // (rank-deficient fronts: more rows reached a front than the full-rank estimate its schedule was cut to)
         P.early_end_failed = true;
         P.evused = 0;
         return fail(STMMQR_ERR_RESCHEDULE, "a front was not finished by its last scheduled panel (the schedule is rebuilt with every panel)");
+    }
+    if (overflow) {
+        if (!P.rh_grow) P.rh_grow = 1;                            // next: the hard bound (QRsym->maxstack / all recycled slabs)
+        else P.overflowed = true;                                 // that too: no recycling for this plan
+        P.arena_overflow = true;
+        P.evused = 0;
+        return fail(STMMQR_ERR_OUT_OF_MEMORY, "the packed factors exceed the R+H arena of the slab recycling");
     }
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, P.ev[0], P.ev[1])); P.stats.ms_h2d = ms;
@@ -1762,10 +1817,6 @@ int stmmqr_factorize_finish(stmmqr_plan *plan, stmmqr_stats *stats)
         fclose(dump);
     }
 
-    // per-front numeric summary (small): flops, ranks
-    P.h_fnum.resize((size_t)std::max(1L, P.nf));
-    if (P.nf > 0)
-        HIPCHK(hipMemcpy(P.h_fnum.data(), P.d_fnum.p, (size_t)P.nf * sizeof(FrontNum), hipMemcpyDeviceToHost));
     double flops = 0, bytes_asm = 0, bytes_pack = 0, fl_upd = 0, fl_upd_pair = 0;
     long rank = 0;
     for (long f = 0; f < P.nf; f++) {
@@ -1774,15 +1825,8 @@ int stmmqr_factorize_finish(stmmqr_plan *plan, stmmqr_stats *stats)
         const FrontSym &s = P.fs[f];
         flops += nm.flops;
         fl_upd += nm.flops_upd;
-        if (getenv("STMMQR_DBG_EARLY") && s.nsched < s.npanels && (!nm.done || nm.g < std::min(nm.fm, s.fn)))
-            fprintf(stderr, "[early] front %ld fn %d fp %d fm %d fm_est %d fm_ub %d g %d rank %d done %d nsched %d npanels %d\n", f, s.fn, s.fp, nm.fm, s.fm_est,
-                    s.fm_ub, nm.g, nm.rank, nm.done, s.nsched, s.npanels);
         if ((size_t)f < P.pair_front.size() && P.pair_front[f]) fl_upd_pair += nm.flops_upd;
         rank += nm.rank;
-        if (nm.perr) {
-            P.panel_wait_failed = true;
-            return fail(STMMQR_ERR_DEVICE, "a panel workgroup gave up waiting for its neighbours (device shared with another job?)");
-        }
         const double cn = s.fn - s.fp, cm = nm.cm;
         const double csize = cm * (cm + 1) / 2 + cm * (cn - cm);
         bytes_asm += 8.0 * ((double)nm.fm * s.fn) + 8.0 * csize;   // F first write + child C read (as a child)
@@ -1878,9 +1922,7 @@ int stmmqr_factorize_device(stmmqr_plan *plan, const stm_long *Ap, const stm_lon
             plan->arena_overflow = false;
             if (g_opt.verbose) fprintf(stderr, "[stmmqr_hip] R+H arena overflow: factorizing again %s\n", plan->overflowed ? "without slab recycling" : "with the arena at its hard bound");
             plan->begun = false;
-            std::vector<int> grp(plan->group.begin(), plan->group.end());
-            for (size_t f = 0; f < grp.size(); f++) if ((size_t)f < plan->shared.size() && plan->shared[f]) grp[f] |= STMMQR_GROUP_SHARED;
-            int e2 = stmmqr_plan_set_groups(plan, grp.data());        // (rh_grow / overflowed: build_schedule sizes the arena anew)
+            int e2 = regroup_same(*plan);                             // (rh_grow / overflowed: build_schedule sizes the arena anew)
             if (e2) return e2;
             arena_retries++;
             attempt = -1;                                             // (both attempts again)
@@ -1893,8 +1935,7 @@ int stmmqr_factorize_device(stmmqr_plan *plan, const stm_long *Ap, const stm_lon
             plan->full_schedule = true;
             if (g_opt.verbose) fprintf(stderr, "[stmmqr_hip] a front outlived its schedule (rank-deficient fronts): factorizing again on the full schedule\n");
             plan->begun = false;
-            std::vector<int> grp(plan->group.begin(), plan->group.end());
-            int e2 = stmmqr_plan_set_groups(plan, grp.data());
+            int e2 = regroup_same(*plan);
             if (e2) return e2;
             reschedules++;
             attempt = -1;
@@ -1920,9 +1961,7 @@ int stmmqr_plan_set_early_end(stmmqr_plan *plan, int mode)
     P.early_end_failed = false;
     P.early_phased = (mode != 0);
     P.full_schedule = (mode == 0);
-    std::vector<int> grp(P.group.begin(), P.group.end());
-    for (size_t f = 0; f < grp.size(); f++) if (f < P.shared.size() && P.shared[f]) grp[f] |= STMMQR_GROUP_SHARED;
-    return stmmqr_plan_set_groups(plan, grp.data());
+    return regroup_same(P);
 }
 
 // ---- multi-GPU support: regroup the fronts, move contribution blocks in and out of a plan --------------

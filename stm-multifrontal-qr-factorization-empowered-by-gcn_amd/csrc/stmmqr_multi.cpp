@@ -504,7 +504,7 @@ int stmmqr_shared_front_gather(stmmqr_plan *plan, stm_long f, int first_rank, in
 
 // One sharded factorization between stmmqr_factorize_begin and stmmqr_factorize_finish as ONE call: per phase the exchange of the
 // blocks that enter it, the shared front this rank takes part in (panel loop + gather) or the rank's own fronts of the phase.
-// The only host waits left are the four bytes stmmqr_factorize_group reads after a group (did a bounded panel wait run out?).
+// The only host waits left are the eight bytes stmmqr_factorize_group reads after a group (did a bounded panel wait run out? abort[2]).
 int stmmqr_factorize_phases(stmmqr_plan *plan, const stmmqr_shard_phases *ph, const stmmqr_transport *tr)
 {
     if (!plan || !plan->begun) return fail(STMMQR_ERR_INVALID, "stmmqr_factorize_begin was not called");

@@ -161,6 +161,7 @@ struct stmmqr_plan {
     long long rh_cap = 0;                // capacity of the R+H arena (doubles)
     long long rh_est_total = 0;          // all packed R+H blocks if no pivot column dies (symbolic; exact for full-rank input)
     int rh_grow = 0;                     // 0: the arena is sized from that estimate; 1: from the hard bounds (it overflowed once)
+    double rh_est_scale = 1.0;           // ... times STMMQR_RH_EST_SCALE, read once when the plan is created (tests shrink the estimate)
     long long scr_doubles = 0;           // scratch of the resident-factor operations: the widest tree level in front form
     std::vector<FrontSym> fs_scr;        // FrontSym with foff into that scratch (kept fronts: their own slab, relative to it)
     bool scr_all = false, scr_valid = false;   // the scratch holds every front (rebuilt once per factorization) / is up to date
@@ -195,7 +196,8 @@ struct stmmqr_plan {
     DevBuf<double> d_msg;                // subtree exchange: message buffers (stmmqr_factorize_exchange, grown on demand)
     DevBuf<int> d_wcnt, d_wcnt2;         // per column block of the update workspaces: slab tickets (zero between launches)
     DevBuf<int> d_wflag, d_wflag2;       // ... fused update: step + 1 once W2 of the column block is in its slot
-    DevBuf<int> d_abort;
+    DevBuf<int> d_abort;                 // [1] a bounded wait ran out, [2] a front outlived its cut schedule, [3] a refused message
+    int abort2_before = 0;               // phased use: abort[2] as the groups run so far left it (reset_group puts it back)
     size_t wcnt_n = 1;
     DevBuf<long long> d_Rboff, d_total;
     DevBuf<long long> d_rhtop, d_fin;    // slab recycling: {bump pointer, overflow word}; Post-order offsets of the packed blocks

@@ -466,6 +466,7 @@ def factorize_sharded(plan, sym: dict, Ax, tol, ntol, comm: Comm, Ap=None, Ai=No
         shard_plan = ShardPlan(plan, sym, owner, phase, comm, span)
     sp = shard_plan
     owner, phase = sp.owner, sp.phase
+    reschedules = 0                                           # (stats["reschedules"] on every path, as the one-plan call reports it)
     if getattr(sp, "early", False):
         from .capi import StmmqrError, ERR_RESCHEDULE
         for attempt in (0, 1):
@@ -483,8 +484,10 @@ def factorize_sharded(plan, sym: dict, Ax, tol, ntol, comm: Comm, Ap=None, Ai=No
             # keeps it (the plan that failed has switched by itself and is told again: harmless)
             sp.early = False
             plan.set_early_end(0)
+            reschedules = attempt + 1
             Ap = Ai = None                                    # (the pattern is set)
     stats = _factorize_sharded_once(plan, sp, Ax, tol, ntol, comm, Ap, Ai, device_ptr)
+    stats["reschedules"] = reschedules
     return stats, owner, phase
 
 

@@ -13,9 +13,13 @@ class Result:
 
 
 class OraclePlan:
-    def __init__(self, S: Symbolic, orc: Oracle):
+    def __init__(self, S: Symbolic, orc: Oracle, reschedule_once: bool = False):
         self.S, self.orc, self.L = S, orc, orc.lib
         self.nf = S.nf
+        # the cut schedule (stmmqr_plan_set_early_end): the oracle has no schedule to cut, it only records the mode.
+        # reschedule_once: the first finish on the cut schedule fails with STMMQR_ERR_RESCHEDULE as a plan whose front outlived
+        # it does, and the plan switches to the full schedule by itself (the library's documented behaviour)
+        self.early, self.reschedule_once, self.nbegin = False, reschedule_once, 0
         self.group = np.zeros(S.nf, np.int32)
         self.shared = np.zeros(S.nf, bool)
         L = self.L
@@ -35,8 +39,12 @@ class OraclePlan:
         self.shared = (g >= 0) & ((g & self.SHARED) != 0)
         self.group = np.where(g >= 0, g & ~self.SHARED, -1).astype(np.int32)
 
+    def set_early_end(self, mode: int):
+        self.early = bool(mode)
+
     def begin(self, Ax, tol, ntol, Ap=None, Ai=None, device_ptr=None):
         S = self.S
+        self.nbegin += 1
         if Ap is not None:
             self.Ap = np.ascontiguousarray(Ap, I64); self.Ai = np.ascontiguousarray(Ai, I64)
         Ax = np.ascontiguousarray(Ax, np.float64)
@@ -231,6 +239,13 @@ class OraclePlan:
         return self.fflops.get(f, 0.0), 0.0
 
     def finish(self):
+        if self.early and self.reschedule_once:
+            import importlib
+            capi = importlib.import_module("stm-multifrontal-qr-factorization-empowered-by-gcn_amd.capi")
+            self.reschedule_once, self.early = False, False
+            e = capi.StmmqrError("stmmqr_factorize_finish failed: a front was not finished by its last scheduled panel (stand-in)")
+            e.code = capi.ERR_RESCHEDULE
+            raise e
         return {"flops": self.flops}
 
     def front_info(self, f):

@@ -10,6 +10,9 @@ from stmmqr_testlib import Symbolic, golden_names, load_golden, numeric_from_gpu
 
 pytestmark = pytest.mark.gpu
 NAMES = golden_names()
+# whole-tree plans whose rank-deficient input makes a front outlive the cut schedule (one reschedule on the first factorization;
+# counted on an MI355X, deterministic: tests/test_gpu_recovery.py pins the fronts); every other fixture has none
+RESCHEDULES = {"lns_3937": 1, "bayer10": 1, "dwt_992": 1}
 
 
 @pytest.fixture(scope="module")
@@ -171,7 +174,7 @@ def test_early_end_schedule_same_bits_and_fallback(pkg, monkeypatch, name, la):
     full_rank = not np.any(A.Rdead)
     if full_rank:
         assert st1["reschedules"] == 0           # (the estimate is exact when no pivot column dies)
-    assert st1["reschedules"] in (0, 1) and st2["reschedules"] == 0
+    assert st1["reschedules"] == RESCHEDULES.get(name, 0) and st2["reschedules"] == 0
     assert st1["flops"] == st0["flops"] == scalar(g, "flopcount")
     for X in (B, C2):
         assert (X.rank, X.rh_total) == (A.rank, A.rh_total)
@@ -294,6 +297,8 @@ def test_panel_wait_timeout_is_recovered(pkg, oracle, monkeypatch, name):
     compare_integers(S, N, g)
     assert G.stats["flops"] == scalar(g, "flopcount")
     assert G.stats["retries"] == 1                      # the recovery is visible in the statistics, never silent
+    if not np.any(G.Rdead):
+        assert G.stats["reschedules"] == 0              # (a wait that ran out is not a front that outlived its schedule)
     No = oracle.factorize(S, g["in_Ap"], g["in_Ai"], g["in_Ax"], scalar(g, "in_tol"), int(scalar(g, "in_ntol")))
     compare_numeric(oracle, S, G, No, g, ftol=1e-10, name=name)
     S2, G2 = gpu_run(pkg, g)

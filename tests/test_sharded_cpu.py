@@ -97,6 +97,23 @@ def test_spread_partition_properties(name, nranks):
         assert int((span > 1).sum()) == 1 and t1 / c1 >= {2: 1.9, 4: 3.5, 8: 6.0}[nranks]
 
 
+def _equals_serial_oracle(S, g, orc, G, flops):
+    """the merged sharded result against the serial oracle, bit for bit (rank 0 of a gloo run)"""
+    from stmmqr_testlib import scalar
+    No = orc.factorize(S, g["in_Ap"], g["in_Ai"], g["in_Ax"], scalar(g, "in_tol"), int(scalar(g, "in_ntol")))
+    nf = S.nf
+    ok = (G.rank == No.c.rank and np.array_equal(G.Hm[:nf], No.Hm[:nf]) and np.array_equal(G.Hr[:nf], No.Hr[:nf])
+          and np.array_equal(G.HStair[:S.rjsize], No.HStair[:S.rjsize])
+          and np.array_equal(G.HPinv[:S.m], No.HPinv[:S.m]) and np.array_equal(G.Rdead[:S.n], No.Rdead[:S.n])
+          and np.array_equal(G.Rblock_off[:nf], No.Rblock_off[:nf]) and G.rh_total == No.c.rh_total
+          and np.array_equal(G.Stack[:G.rh_total], No.Stack[:No.c.rh_total])
+          and np.array_equal(G.HTau[:S.rjsize], No.HTau[:S.rjsize]) and G.maxfm == No.c.maxfm)
+    for f in range(nf):
+        a = S.Hip[f]
+        ok = ok and np.array_equal(G.Hii[a:a + G.Hm[f]], No.Hii[a:a + No.Hm[f]])
+    return bool(ok and flops == No.c.flopcount)                # a shared front is counted once
+
+
 def _worker(rank, world, port, name, spread, q):
     sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
     import torch.distributed as dist
@@ -123,18 +140,7 @@ def _worker(rank, world, port, name, spread, q):
         fl = torch.tensor([st["flops"]], dtype=torch.float64)
         dist.all_reduce(fl)
         if rank == 0:
-            No = orc.factorize(S, g["in_Ap"], g["in_Ai"], g["in_Ax"], scalar(g, "in_tol"), int(scalar(g, "in_ntol")))
-            nf = S.nf
-            ok = (G.rank == No.c.rank and np.array_equal(G.Hm[:nf], No.Hm[:nf]) and np.array_equal(G.Hr[:nf], No.Hr[:nf])
-                  and np.array_equal(G.HStair[:S.rjsize], No.HStair[:S.rjsize])
-                  and np.array_equal(G.HPinv[:S.m], No.HPinv[:S.m]) and np.array_equal(G.Rdead[:S.n], No.Rdead[:S.n])
-                  and np.array_equal(G.Rblock_off[:nf], No.Rblock_off[:nf]) and G.rh_total == No.c.rh_total
-                  and np.array_equal(G.Stack[:G.rh_total], No.Stack[:No.c.rh_total])
-                  and np.array_equal(G.HTau[:S.rjsize], No.HTau[:S.rjsize]) and G.maxfm == No.c.maxfm)
-            for f in range(nf):
-                a = S.Hip[f]
-                ok = ok and np.array_equal(G.Hii[a:a + G.Hm[f]], No.Hii[a:a + No.Hm[f]])
-            ok = ok and float(fl[0]) == No.c.flopcount            # a shared front is counted once
+            ok = _equals_serial_oracle(S, g, orc, G, float(fl[0]))
             ncross = len(sh.cross_edges(sym, owner, phase))
             q.put((bool(ok), int((phase > 0).sum()), ncross, 0 if sp is None else int((sp.span > 1).sum())))
         done = True
@@ -191,3 +197,62 @@ def test_failed_rank_ends_the_run_instead_of_hanging_it():
     with pytest.raises(AssertionError, match="rank exit codes"):
         run_ranks(_failing_worker, 2, (), timeout=120)
     assert time.monotonic() - t0 < 60
+
+
+def _reschedule_worker(rank, world, port, name, spread, force_rank, early_env, q):
+    sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
+    import os
+    import torch
+    import torch.distributed as dist
+    from oracle_plan import OraclePlan
+    from stmmqr_testlib import Oracle, Symbolic, finish_ranks, load_golden, scalar
+    if early_env is not None:
+        os.environ["STMMQR_EARLY_END_SHARDED"] = early_env
+    sh = shard_mod()
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    done = False
+    try:
+        g = load_golden(name)
+        S = Symbolic(g)
+        sym = sym_dict(S)
+        orc = Oracle()
+        comm = sh.Comm(dist)
+        plan = OraclePlan(S, orc, reschedule_once=(rank == force_rank))
+        if spread:
+            owner, phase, span = sh.spread_partition(sym, world, **SPREAD_SMALL)
+        else:
+            (owner, phase), span = sh.partition(sym, world), None
+        sp = sh.ShardPlan(plan, sym, owner, phase, comm, span)
+        st, owner, phase = sh.factorize_sharded(plan, sym, g["in_Ax"], scalar(g, "in_tol"), int(scalar(g, "in_ntol")), comm,
+                                                Ap=g["in_Ap"], Ai=g["in_Ai"], shard_plan=sp)
+        G = sh.gather_numeric(plan, sym, comm, owner, shard_plan=sp)
+        # per rank: was the key there, its value, how many times the rank began a factorization, is the plan still on the cut schedule
+        mine = torch.tensor([int("reschedules" in st), int(st.get("reschedules", -1)), plan.nbegin, int(plan.early)], dtype=torch.int64)
+        every = [torch.zeros(4, dtype=torch.int64) for _ in range(world)]
+        dist.all_gather(every, mine)
+        fl = torch.tensor([st["flops"]], dtype=torch.float64)
+        dist.all_reduce(fl)
+        if rank == 0:
+            q.put((_equals_serial_oracle(S, g, orc, G, float(fl[0])), [[int(x) for x in t] for t in every]))
+        done = True
+    finally:
+        finish_ranks(dist, done)
+
+
+@pytest.mark.parametrize("name,world,spread", [("syn_rankdef_grid", 2, False), ("epb1", 4, False), ("grid20_standin", 2, True)])
+@pytest.mark.parametrize("force_rank,early_env", [(None, None), (0, None), (1, None), ("last", None), (None, "0")])
+def test_reschedule_agreement_through_factorize_sharded(name, world, spread, force_rank, early_env):
+    """The agreement protocol of the cut schedule (sharded.factorize_sharded) with the oracle stand-in: when ONE rank's finish says
+    STMMQR_ERR_RESCHEDULE, every rank factorizes again on the full schedule; stats["reschedules"] is present and the same on every
+    rank (1 when forced, 0 otherwise -- also with the cut schedule off, STMMQR_EARLY_END_SHARDED=0), and the merged result is the
+    serial oracle's bit for bit"""
+    from stmmqr_testlib import run_ranks
+    fr = world - 1 if force_rank == "last" else force_rank
+    ok, every = run_ranks(_reschedule_worker, world, (name, spread, fr, early_env), timeout=300)
+    assert ok
+    want = 1 if fr is not None else 0
+    for has_key, resched, nbegin, early in every:
+        assert has_key == 1
+        assert resched == want
+        assert nbegin == 1 + want                             # every rank runs again, not only the one that failed
+        assert early == (1 if (want == 0 and early_env is None) else 0)   # after a reschedule every rank keeps the full schedule
