@@ -150,6 +150,11 @@ typedef struct stmmqr_symbolic_view {
     const stm_long *Child, *Childp, *Super, *Rp, *Rj, *Post, *Hip, *Fm;
     stm_long maxstack;          /* QRsym->maxstack: the analysis' bound for the reference's one stack, hence for all of R+H; sizes the
                                    R+H arena of the slab recycling.  0 = unknown (the arena then holds all recycled slabs)          */
+    stm_long r_only;            /* !QRsym->keepH.  0 (a zero-initialised view): the Householder vectors are kept (R+H blocks), as
+                                   always.  1: R only, in qr_rhpack's keepH = 0 layout -- less device memory and a smaller download;
+                                   stmmqr_plan_rsolve and the seminormal solve work, everything that needs Q (qmult, solve, H of
+                                   export_r) returns STMMQR_ERR_INVALID, and the plan takes one group only (stmmqr_plan_set_groups,
+                                   the shared-front and phase entries refuse it) */
 } stmmqr_symbolic_view;
 
 /* per-call measurements (all times in milliseconds, HIP events on the library's own stream) */
@@ -368,6 +373,24 @@ int stmmqr_plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *
  *                      X = R'\B, 3 QR_RTX_EQUALS_ETB  X = R'\(E'B) -- B n x nrhs, X m x nrhs (zero beyond the rank). */
 int stmmqr_plan_rsolve(stmmqr_plan *plan, int system, const double *B, stm_long ldb, double *X, stm_long ldx,
                        stm_long nrhs);
+/* Factors without H (stmmqr_symbolic_view.r_only = 1, QRsym->keepH = 0): stmmqr_plan_rsolve takes all four systems;
+ * stmmqr_plan_qmult and stmmqr_plan_solve return STMMQR_ERR_INVALID (the message names keepH) and leave the plan usable.
+ *   stmmqr_plan_keep_h           1 / 0: the plan's keepH (-1: null plan).
+ *   stmmqr_plan_spmv             Y = A X (trans 0: X n x nrhs, Y m x nrhs) or Y = A' X (trans 1: X m x nrhs, Y n x nrhs) with the
+ *                                values of the last factorization and A's pattern as given to it (A's own row and column order).
+ *                                on_device: X and Y are device pointers, else host arrays.  Deterministic: every entry is summed
+ *                                in index order, no atomics, so column j of a batch equals the single-vector call.
+ *   stmmqr_plan_solve_seminormal least squares with R only, by the corrected seminormal equations: x = E R^-1 R^-T E' A'b, then
+ *                                `refine` times r = b - A x, x += E R^-1 R^-T E' A'r (B m x nrhs, X n x nrhs; device pointers
+ *                                with on_device).  Works on plans with and without H and reads R only.  Dead columns get x = 0
+ *                                (the basic solution).  info (may be NULL): the largest |A'r| / (|A|_F (|A|_F |x| + |b|)) over the
+ *                                right-hand sides, r = b - A x of the returned x.  Accurate to about cond(A) u only while
+ *                                cond(A)^2 u << 1: above cond(A) ~ 1e7 the Q-based stmmqr_plan_solve is the right tool.  A front too
+ *                                wide for the one-workgroup R' solve gives STMMQR_ERR_TOO_LARGE, as stmmqr_plan_rsolve systems 2-3. */
+int stmmqr_plan_keep_h(const stmmqr_plan *plan);
+int stmmqr_plan_spmv(stmmqr_plan *plan, int trans, const double *X, stm_long ldx, double *Y, stm_long ldy, stm_long nrhs, int on_device);
+int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int refine,
+                                 int on_device, double *info);
 
 /* dense single-front kernels on host buffers (inner seams without the cc argument) */
 stm_long stmmqr_front(stm_long m, stm_long n, stm_long npiv, double tol, stm_long ntol, double *F,
@@ -495,6 +518,14 @@ int stmmqr_sparseqr(int ordering, double tol, stm_long m, stm_long n, const stm_
 int stmmqr_sparseqr_symbolic(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai,
                              const double *Ax, const stm_long *Quser, const stmmqr_relax *relax, stmmqr_qr **out);
 int stmmqr_sparseqr_numeric(stmmqr_qr *qr, int device);
+/* keep = 0 between stmmqr_sparseqr_symbolic and _numeric: the numeric phase keeps R only (keepH = 0); stmmqr_sparseqr_solve works,
+ * stmmqr_sparseqr_qmult returns STMMQR_ERR_INVALID */
+int stmmqr_sparseqr_set_keep_h(stmmqr_qr *qr, int keep);
+/* least squares by the corrected seminormal equations (stmmqr_plan_solve_seminormal) on a factorized object, with or without H:
+ * A (Ap, Ai, Ax) is the caller's full matrix, the one factorized (products with it run on the device); R'\ and R\ are systems 3
+ * and 1 of stmmqr_sparseqr_solve.  B m x nrhs, X n x nrhs (host arrays); info (may be NULL) as for the plan */
+int stmmqr_sparseqr_solve_seminormal(stmmqr_qr *qr, const stm_long *Ap, const stm_long *Ai, const double *Ax, const double *B, stm_long ldb,
+                                     stm_long nrhs, double *X, stm_long ldx, int refine, double *info);
 void stmmqr_sparseqr_free(stmmqr_qr *qr);
 /* info[0..11] = rank, n1rows, n1cols, nf, analyze seconds (ordering + analysis: Ana_time), factorize seconds (the qr_factorize
  * interval: Fac_time), flops (the reference's count), flop bound, device ms of the factorization, ordering used,

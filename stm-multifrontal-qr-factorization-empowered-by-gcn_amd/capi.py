@@ -61,7 +61,7 @@ lib = C.CDLL(str(lib_path))
 class SymbolicView(C.Structure):
     _fields_ = [(k, C.c_long) for k in ["m", "n", "anz", "nf", "maxfn", "rjsize", "hisize", "do_rank_detection"]] + \
                [(k, c_long_p) for k in ["Sp", "Sj", "Qfill", "PLinv", "Sleft", "Child", "Childp", "Super", "Rp", "Rj",
-                                        "Post", "Hip", "Fm"]] + [("maxstack", C.c_long)]
+                                        "Post", "Hip", "Fm"]] + [("maxstack", C.c_long), ("r_only", C.c_long)]
 
 
 class Stats(C.Structure):
@@ -146,6 +146,13 @@ lib.stmmqr_plan_front_flops.argtypes = [C.c_void_p, C.c_long, c_double_p]
 lib.stmmqr_plan_device_bytes.argtypes = [C.c_void_p]
 lib.stmmqr_plan_device_bytes.restype = C.c_double
 lib.stmmqr_plan_solve.argtypes = [C.c_void_p, c_double_p, C.c_long, c_double_p, C.c_long, C.c_long]
+lib.stmmqr_plan_keep_h.argtypes = [C.c_void_p]
+lib.stmmqr_plan_spmv.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int]
+lib.stmmqr_plan_solve_seminormal.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int,
+                                             c_double_p]
+lib.stmmqr_sparseqr_set_keep_h.argtypes = [C.c_void_p, C.c_int]
+lib.stmmqr_sparseqr_solve_seminormal.argtypes = [C.c_void_p, c_long_p, c_long_p, c_double_p, c_double_p, C.c_long, C.c_long, c_double_p,
+                                                 C.c_long, C.c_int, c_double_p]
 lib.stmmqr_get_options.argtypes = [C.POINTER(Options)]
 lib.stmmqr_set_options.argtypes = [C.POINTER(Options)]
 
@@ -318,6 +325,7 @@ class HipQR:
                 self._keep[k] = a
             setattr(v, k, _ip(a))
         v.maxstack = int(sym.get("maxstack", 0) or 0)
+        v.r_only = 0 if sym.get("keepH") is None or int(sym["keepH"]) else 1     # (keepH = 0: R only, qr_rhpack's keepH = 0 layout)
         self.sym = {k: int(sym[k]) for k in ["m", "n", "anz", "nf", "maxfn", "rjsize", "hisize"]}
         st = C.c_int(0)
         self._h = lib.stmmqr_plan_create(C.byref(v), device, C.byref(st))
@@ -538,6 +546,32 @@ class HipQR:
         _check(lib.stmmqr_plan_rsolve(self._h, int(system), _dp(Bf), br, _dp(X), xr, Bf.shape[1]), "stmmqr_plan_rsolve")
         return X[:, 0] if np.ndim(B) == 1 else X
 
+    @property
+    def keep_h(self) -> bool:
+        """False when the plan keeps R only (sym["keepH"] = 0)"""
+        return bool(lib.stmmqr_plan_keep_h(self._h))
+
+    def spmv(self, X: np.ndarray, trans: int = 0) -> np.ndarray:
+        """A X (trans 0: X n or n x nrhs) or A' X (trans 1: X m or m x nrhs) on the device, with the values of the last
+        factorization.  Deterministic: column j of a batch equals the single-vector call."""
+        m, n = self.sym["m"], self.sym["n"]
+        xr, yr = (m, n) if trans else (n, m)
+        Xf = np.array(X, dtype=np.float64, order="F", copy=True).reshape(xr, -1, order="F")
+        Y = np.zeros((yr, Xf.shape[1]), order="F")
+        _check(lib.stmmqr_plan_spmv(self._h, int(trans), Xf.ctypes.data, xr, Y.ctypes.data, yr, Xf.shape[1], 0), "stmmqr_plan_spmv")
+        return Y[:, 0] if np.ndim(X) == 1 else Y
+
+    def solve_seminormal(self, B: np.ndarray, refine: int = 1):
+        """Least squares with R only, by the corrected seminormal equations x = E R^-1 R^-T E' A'b plus `refine` correction steps.
+        Returns (X, info), info = max over the columns of |A'r| / (|A|_F (|A|_F |x| + |b|)).  Accurate while cond(A)^2 u << 1."""
+        m, n = self.sym["m"], self.sym["n"]
+        Bf = np.array(B, dtype=np.float64, order="F", copy=True).reshape(m, -1, order="F")
+        X = np.zeros((n, Bf.shape[1]), order="F")
+        info = C.c_double(0)
+        _check(lib.stmmqr_plan_solve_seminormal(self._h, Bf.ctypes.data, m, X.ctypes.data, n, Bf.shape[1], int(refine), 0, C.byref(info)),
+               "stmmqr_plan_solve_seminormal")
+        return (X[:, 0] if np.ndim(B) == 1 else X), float(info.value)
+
     def solve(self, B: np.ndarray) -> np.ndarray:
         """QR_solve(QR_RETX_EQUALS_B) (SparseQR.h:411-417): X = E R^-1 (Q'B)(1:n), least-squares solution; rank == n only."""
         m, n = self.sym["m"], self.sym["n"]
@@ -675,10 +709,10 @@ def qr_cpack(m, n, npiv, g, F):
     return int(cm), Cp[:qr_fcsize(m, n, npiv, g)]
 
 
-def qr_rhpack(m, n, npiv, Stair, F):
-    """qr_rhpack with keepH (SparseQR.h:244-253): returns (rsize, rm, packed R+H)."""
+def qr_rhpack(m, n, npiv, Stair, F, keep_h=True):
+    """qr_rhpack (SparseQR.h:244-253): returns (rsize, rm, packed R+H), or packed R only with keep_h=False."""
     R = np.zeros(max(m * n, 1)); rm = C.c_long(0)
-    rs = lib.qr_rhpack(1, m, n, npiv, _ip(Stair), _dp(F), _dp(R), C.byref(rm))
+    rs = lib.qr_rhpack(1 if keep_h else 0, m, n, npiv, _ip(Stair), _dp(F), _dp(R), C.byref(rm))
     if rs < 0:
         raise StmmqrError("qr_rhpack failed")
     return int(rs), int(rm.value), R[:rs]
@@ -810,15 +844,21 @@ class SparseQR:
     alone: singletons + COLAMD + symbolic analysis on the host, numeric factorization and the Q / R operations on the device.
     symbolic_only=True stops after the host half (no GPU needed)."""
 
-    def __init__(self, m, n, Ap, Ai, Ax, ordering=7, tol=-2.0, relax: Relax | None = None, Quser=None, device=-1, symbolic_only=False):
+    def __init__(self, m, n, Ap, Ai, Ax, ordering=7, tol=-2.0, relax: Relax | None = None, Quser=None, device=-1, symbolic_only=False,
+                 keep_h=True):
+        """keep_h=False: the numeric phase keeps R only (keepH = 0): solve works, qmult and export_r's H do not."""
         self.m, self.n = int(m), int(n)
         self._A = (np.ascontiguousarray(Ap, I64), np.ascontiguousarray(Ai, I64), np.ascontiguousarray(Ax, np.float64))
         Q = None if Quser is None else np.ascontiguousarray(Quser, I64)
         self._h = C.c_void_p()
         rp = None if relax is None else C.byref(relax)
-        if symbolic_only:
+        if symbolic_only or not keep_h:
             _check(lib.stmmqr_sparseqr_symbolic(ordering, tol, m, n, _ip(self._A[0]), _ip(self._A[1]), _dp(self._A[2]), _ip(Q), rp,
                                                 C.byref(self._h)), "stmmqr_sparseqr_symbolic")
+            if not keep_h:
+                _check(lib.stmmqr_sparseqr_set_keep_h(self._h, 0), "stmmqr_sparseqr_set_keep_h")
+                if not symbolic_only:
+                    self.numeric(device)
         else:
             _check(lib.stmmqr_sparseqr(ordering, tol, m, n, _ip(self._A[0]), _ip(self._A[1]), _dp(self._A[2]), _ip(Q), rp, device,
                                        C.byref(self._h)), "stmmqr_sparseqr")
@@ -885,6 +925,7 @@ class SparseQR:
     def lq(cls, m, n, Ap, Ai, Ax, tol=-2.0, relax: Relax | None = None, device=-1):
         """SparseLQ (SparseLQ.c:691-734): the QR object of A' (L = R')."""
         self = cls.__new__(cls)
+        self._is_lq = True                                   # (the QR object of A': solve_seminormal would need A' as the matrix)
         self.m, self.n = int(n), int(m)
         self._A = (np.ascontiguousarray(Ap, I64), np.ascontiguousarray(Ai, I64), np.ascontiguousarray(Ax, np.float64))
         self._h = C.c_void_p()
@@ -899,6 +940,21 @@ class SparseQR:
         Y = np.zeros_like(X, order="F")
         _check(lib.stmmqr_sparseqr_qmult(self._h, method, _dp(X), X.shape[0], X.shape[0], X.shape[1], _dp(Y), Y.shape[0]), "stmmqr_sparseqr_qmult")
         return Y
+
+    def solve_seminormal(self, B, refine=1):
+        """Least squares by the corrected seminormal equations with R only (also without H), products with this object's full A on
+        the device.  Returns (X, info), info = max over the columns of |A'r| / (|A|_F (|A|_F |x| + |b|))."""
+        if getattr(self, "_is_lq", False):
+            raise StmmqrError("solve_seminormal: not on the LQ object")
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim == 1:
+            B = B.reshape(-1, 1, order="F")
+        X = np.zeros((self.n, B.shape[1]), order="F")
+        info = C.c_double(0)
+        _check(lib.stmmqr_sparseqr_solve_seminormal(self._h, _ip(self._A[0]), _ip(self._A[1]), _dp(self._A[2]), _dp(B), B.shape[0],
+                                                    B.shape[1], _dp(X), self.n, int(refine), C.byref(info)),
+               "stmmqr_sparseqr_solve_seminormal")
+        return X, float(info.value)
 
     def solve(self, system, B):
         B = np.asfortranarray(B, dtype=np.float64)

@@ -173,6 +173,9 @@ int stmmqr_plan_export_r(stmmqr_plan *plan, const stm_qr_symbolic *S, stm_long e
 {
     if (!plan || !S || !Rp_out || !Ri_out || !Rx_out) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_plan_export_r: null argument");
     try {
+        const bool wantH = nh_out && Hp_out && Hi_out && Hx_out && HTau_out;
+        const int keepH = stmmqr_plan_keep_h(plan);
+        if (wantH && !keepH) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_plan_export_r: the plan keeps no Householder vectors (keepH = 0)");
         stm_long rh_total = 0, rank = 0;
         int e = stmmqr_plan_result_sizes(plan, &rh_total, &rank);
         if (e) return e;
@@ -189,9 +192,8 @@ int stmmqr_plan_export_r(stmmqr_plan *plan, const stm_qr_symbolic *S, stm_long e
         for (Long f = 0; f < nf; f++) Rblock[(size_t)f] = Stack.data() + off[(size_t)f];
         stm_qr_numeric N;
         memset(&N, 0, sizeof N);
-        N.Rblock = Rblock.data(); N.keepH = 1; N.Rdead = Rdead.data(); N.HStair = HStair.data(); N.HTau = HTau.data(); N.Hii = Hii.data();
+        N.Rblock = Rblock.data(); N.keepH = keepH; N.Rdead = Rdead.data(); N.HStair = HStair.data(); N.HTau = HTau.data(); N.Hii = Hii.data();
         N.Hm = Hm.data(); N.Hr = Hr.data(); N.nf = nf; N.n = n; N.m = m;
-        const bool wantH = nh_out && Hp_out && Hi_out && Hx_out && HTau_out;
         Long *Rp = (Long *)calloc((size_t)n + 1, sizeof(Long));
         Long *Hp = wantH ? (Long *)calloc((size_t)std::max<Long>(S->rjsize, 1) + 1, sizeof(Long)) : nullptr;
         if (!Rp || (wantH && !Hp)) { free(Rp); free(Hp); return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_plan_export_r: out of memory"); }

@@ -608,6 +608,14 @@ void build_schedule(stmmqr_plan &P, std::vector<int> &tslot)
             for (long f = 0; f < nf; f++) bysize[(size_t)f] = (int)f;
             std::stable_sort(bysize.begin(), bysize.end(), [&](int a, int b) {
                 return (long long)P.fs[a].ld * P.fs[a].fn > (long long)P.fs[b].ld * P.fs[b].fn; });
+            // R only (keepH = 0): the arena holds the estimated R of the fronts that do not keep their slab (+ 12.5 %); a kept
+            // front's R is packed on the fly by the download and never enters it
+            auto staged_est = [&](const std::vector<char> &kp) -> long long {
+                double e = 0;
+                for (long f = 0; f < nf; f++) if (!kp[(size_t)f]) e += (double)P.rh_est_front[(size_t)f];
+                const long long est = (long long)(e * P.rh_est_scale);
+                return est + est / 8 + 4096;
+            };
             long long best = -1;
             int bestk = 0;
             for (int k = 0; k <= std::min(3L, nf); k++) {
@@ -616,7 +624,8 @@ void build_schedule(stmmqr_plan &P, std::vector<int> &tslot)
                 for (int q = 0; q < k; q++) kp[(size_t)bysize[(size_t)q]] = 1;
                 for (long f = 0; f < nf; f++) if (!kp[(size_t)f]) rec += (long long)P.fs[f].ld * P.fs[f].fn;
                 const auto pk = timeline_offsets(P, kp, nstep, false);
-                const long long cap = (P.maxstack > 0) ? std::min((long long)P.maxstack, rec) : rec;
+                long long cap = (P.maxstack > 0) ? std::min((long long)P.maxstack, rec) : rec;
+                if (!P.keep_h && !P.rh_grow) cap = std::min(cap, staged_est(kp));     // (R only: the arena follows the packed R)
                 const long long tot = pk.first + pk.second + cap;
                 if (best < 0 || tot < best - best / 50) { best = tot; bestk = k; }      // (a kept front must buy at least 2 %)
             }
@@ -628,7 +637,8 @@ void build_schedule(stmmqr_plan &P, std::vector<int> &tslot)
             // (the estimate + 12.5 % where that is less: dead columns move rows into later fronts and can make the factors
             //  larger than the full-rank pattern says; an arena that overflows is regrown to the hard bound and the factorization
             //  repeated once -- stats.retries says so)
-            if (!P.rh_grow && P.rh_est_total > 0) {
+            if (!P.rh_grow && !P.keep_h) P.rh_cap = std::max(1LL, std::min(P.rh_cap, staged_est(P.kept)));
+            else if (!P.rh_grow && P.rh_est_total > 0) {
                 // (P.rh_est_scale: tests shrink the estimate to drive the overflow path)
                 const long long est = (long long)((double)P.rh_est_total * P.rh_est_scale);
                 P.rh_cap = std::max(1LL, std::min(P.rh_cap, est + est / 8 + 4096));
@@ -708,6 +718,7 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
 {
     P.m = v.m; P.n = v.n; P.anz = v.anz; P.nf = v.nf; P.maxfn = v.maxfn; P.rjsize = v.rjsize;
     P.hisize = v.hisize; P.do_rank = v.do_rank_detection ? 1 : 0;
+    P.keep_h = v.r_only ? 0 : 1;
     P.maxstack = v.maxstack > 0 ? v.maxstack : 0;
     // (a plan-time knob that every later rebuild of the schedule keeps: a reschedule must not give the plan another arena)
     P.rh_est_scale = getenv("STMMQR_RH_EST_SCALE") ? atof(getenv("STMMQR_RH_EST_SCALE")) : 1.0;
@@ -817,6 +828,7 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
     // C) run through qr_front's row bookkeeping (:1434-1609) and qr_rhpack's column lengths (:1691-1784).  Sizes the R+H arena of
     // the slab recycling (with a margin; QRsym->maxstack is the hard bound the arena falls back to) ----
     P.rh_est_total = 0;
+    P.rh_est_front.assign((size_t)std::max(1L, nf), 0);
     {
         std::vector<long> stair;
         for (long kf = 0; kf < nf; kf++) {
@@ -837,10 +849,12 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
                 long t;
                 if (g >= fm) t = (k < fp) ? 0 : fm;                       // rows ran out
                 else { t = std::min(fm, std::max(g + 1, stair[(size_t)k])); g++; }
+                if (!P.keep_h) { if (k < fp && t > 0 && rm < fm) rm++; sz += rm; continue; }   // (R only: rm rows per column)
                 if (k < fp) { if (t > 0) rm++; sz += (t > 0) ? t : rm; }
                 else { const long h = std::min(rm + (k - fp) + 1, fm); sz += rm + std::max(t - h, 0L); }
             }
             P.rh_est_total += sz;
+            P.rh_est_front[(size_t)f] = sz;
         }
     }
 
@@ -930,6 +944,8 @@ int set_pattern(stmmqr_plan &P, const stm_long *Ap, const stm_long *Ai)
     if (P.anz > 0)
         HIPCHK(hipMemcpyAsync(P.d_smap.p, smap.data(), (size_t)P.anz * sizeof(int), hipMemcpyHostToDevice, P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));
+    P.h_smap.swap(smap);                                     // (the products with A rebuild A's pattern from it: stm_ensure_a_index)
+    P.a_index_ready = false;
     P.pattern_set = true;
     return 0;
 }
@@ -1142,8 +1158,13 @@ int run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req = null
             if (P.recycle && S.n_rhp > 0) {
                 // slab recycling: the packed R+H blocks of the fronts that are finished now go to the arena (sizes and places on the
                 // device: k_rh_count bumps the arena's pointer); their slabs are free from the next step on
-                LCHK(stm_launch_rh_count(c, L0 + S.rhp_off, S.n_rhp, q));
-                LCHK(stm_launch_rh_copy(c, L0 + S.rhp_off, L0 + S.rhp_parts_off, S.n_rhp, S.rhp_maxparts, P.d_RH.p, q));
+                if (P.keep_h) {
+                    LCHK(stm_launch_rh_count(c, L0 + S.rhp_off, S.n_rhp, q));
+                    LCHK(stm_launch_rh_copy(c, L0 + S.rhp_off, L0 + S.rhp_parts_off, S.n_rhp, S.rhp_maxparts, P.d_RH.p, q));
+                } else {
+                    LCHK(stm_launch_r_count(c, L0 + S.rhp_off, S.n_rhp, q));
+                    LCHK(stm_launch_r_copy(c, L0 + S.rhp_off, L0 + S.rhp_parts_off, S.n_rhp, S.rhp_maxparts, P.d_RH.p, q));
+                }
                 nlaunch += 2;
             }
             return 0;
@@ -1418,7 +1439,7 @@ int run_pack(stmmqr_plan &P, bool &overflow)
             LCHK(d_kl.upload(kl, st));
             DevCtx ck = c;
             ck.rh_top = nullptr;                                  // (no place in the arena: packed on the fly by the download)
-            LCHK(stm_launch_rh_count(ck, d_kl.p, (int)kl.size(), st));
+            LCHK(P.keep_h ? stm_launch_rh_count(ck, d_kl.p, (int)kl.size(), st) : stm_launch_r_count(ck, d_kl.p, (int)kl.size(), st));
             HIPCHK(hipStreamSynchronize(st));
         }
         LCHK(stm_launch_rh_scan(c, L0 + P.post_off, (int)P.nf, P.d_total.p, P.d_fin.p, st));
@@ -1431,14 +1452,15 @@ int run_pack(stmmqr_plan &P, bool &overflow)
         overflow = (top[1] != 0);
         return 0;
     }
-    LCHK(stm_launch_rh_count(c, L0 + P.own_off, P.n_own, st));
+    LCHK(P.keep_h ? stm_launch_rh_count(c, L0 + P.own_off, P.n_own, st) : stm_launch_r_count(c, L0 + P.own_off, P.n_own, st));
     LCHK(stm_launch_rh_scan(c, L0 + P.post_off, (int)P.nf, P.d_total.p, P.d_Rboff.p, st));
     long long total = 0;
     HIPCHK(hipMemcpyAsync(&total, P.d_total.p, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     P.rh_total = total;
     if ((size_t)total > P.d_RH.n) LCHK(P.d_RH.alloc((size_t)(total + total / 64 + 1024)));   // (a little room: a refactorization with other dead columns)
-    LCHK(stm_launch_rh_copy(c, L0 + P.own_off, L0 + P.rh_parts_off, P.n_own, P.rh_maxparts, P.d_RH.p, st));
+    if (P.keep_h) LCHK(stm_launch_rh_copy(c, L0 + P.own_off, L0 + P.rh_parts_off, P.n_own, P.rh_maxparts, P.d_RH.p, st));
+    else LCHK(stm_launch_r_copy(c, L0 + P.own_off, L0 + P.rh_parts_off, P.n_own, P.rh_maxparts, P.d_RH.p, st));
     P.stats.nlaunch += 3;
     return 0;
 }
@@ -1448,6 +1470,38 @@ int run_pack(stmmqr_plan &P, bool &overflow)
 // (what the other host translation units need of the planner / scheduler: stmmqr_plan.h)
 int stm_run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req) { return run_schedule(P, detail, grp, req); }
 int stm_ensure_device(int device) { return ensure_device(device); }
+
+// Products with A (stmmqr_plan_spmv, the seminormal solve): A's column form and a row form whose entries point at A's values,
+// built at the first such call after set_pattern from the plan's S pattern and the S -> A map (S = A(P, Q), smap[S entry] =
+// position in A); the factorization itself never needs them.  Rows keep A's column order.
+int stm_ensure_a_index(stmmqr_plan &P)
+{
+    if (P.a_index_ready) return 0;
+    if (!P.pattern_set) return fail(STMMQR_ERR_INVALID, "pattern of A was never given");
+    const long m = P.m, n = P.n, anz = P.anz;
+    std::vector<int> rowof((size_t)std::max(1L, m)), arow((size_t)std::max(1L, anz)), acol((size_t)std::max(1L, anz));
+    for (long i = 0; i < m; i++) rowof[(size_t)P.PLinv[i]] = (int)i;
+    for (long r = 0; r < m; r++)
+        for (long q = P.Sp[r]; q < P.Sp[r + 1]; q++) {
+            const int p = P.h_smap[(size_t)q];
+            arow[(size_t)p] = rowof[(size_t)r];
+            acol[(size_t)p] = (int)(P.has_qfill ? P.Qfill[P.Sj[q]] : P.Sj[q]);
+        }
+    std::vector<int> acp((size_t)n + 1, 0), arp((size_t)m + 1, 0), arj((size_t)std::max(1L, anz)), arq((size_t)std::max(1L, anz));
+    for (long p = 0; p < anz; p++) { acp[(size_t)acol[(size_t)p] + 1]++; arp[(size_t)arow[(size_t)p] + 1]++; }
+    for (long j = 0; j < n; j++) acp[(size_t)j + 1] += acp[(size_t)j];
+    for (long i = 0; i < m; i++) arp[(size_t)i + 1] += arp[(size_t)i];
+    std::vector<int> next(arp.begin(), arp.end() - 1);
+    for (long p = 0; p < anz; p++) {                         // (A's order: column by column, so every row in column order)
+        const int q = next[(size_t)arow[(size_t)p]]++;
+        arj[(size_t)q] = acol[(size_t)p]; arq[(size_t)q] = (int)p;
+    }
+    LCHK(P.d_Acp.upload(acp, P.stream)); LCHK(P.d_Aci.upload(arow, P.stream));
+    LCHK(P.d_Arp.upload(arp, P.stream)); LCHK(P.d_Arj.upload(arj, P.stream)); LCHK(P.d_Arq.upload(arq, P.stream));
+    HIPCHK(hipStreamSynchronize(P.stream));
+    P.a_index_ready = true;
+    return 0;
+}
 
 // The schedule rebuilt on the plan's own grouping (after a factorization that asked for another schedule: the full one, a larger
 // arena, the cut one on or off).  P.group holds the group ids only; the shared fronts get their STMMQR_GROUP_SHARED bit back, or
@@ -1591,6 +1645,9 @@ int stmmqr_factorize_begin(stmmqr_plan *plan, const stm_long *Ap, const stm_long
         if (e) return e;
     }
     if (!P.pattern_set) return fail(STMMQR_ERR_INVALID, "pattern of A was never given");
+    if (!P.keep_h)
+        for (long f = 0; f < P.nf; f++)
+            if (P.group[f] != 0) return fail(STMMQR_ERR_INVALID, "a plan without H (keepH = 0) takes one group only");
     if (((P.early_end && !P.early_phased) || P.early_end_failed) && !P.whole_call) {
         // phased use (begin / group / finish by the caller): no retry loop around the factorization, so the plan schedules every
         // panel of every front (the cut schedule needs stmmqr_factorize_device's rerun when a front outlives it)
@@ -1656,7 +1713,8 @@ int stmmqr_factorize_group(stmmqr_plan *plan, int group, int detail)
                             (long long)envl("STMMQR_LA_FUSED_ROWS", 5120), (long long)envl("STMMQR_LA_MAXPWG", 48), (long long)envl("STMMQR_LA_SYSFENCE", 0),
                             (long long)envl("STMMQR_SIDE_RESERVE", 32), (long long)envl("STMMQR_PASSENGERS", 1), (long long)envl("STMMQR_PASS_ROWS", 16384),
                             (long long)envl("STMMQR_PASS_MAXWG", 384), (long long)envl("STMMQR_PASS_TILES", 1L << 40), (long long)envl("STMMQR_CA_RIDERS", 1),
-                            (long long)envl("STMMQR_PASS_ABL", 0), (long long)std::hash<std::string>()(getenv("STMMQR_PASS_K") ? getenv("STMMQR_PASS_K") : "")})
+                            (long long)envl("STMMQR_PASS_ABL", 0), (long long)std::hash<std::string>()(getenv("STMMQR_PASS_K") ? getenv("STMMQR_PASS_K") : ""),
+                            (long long)P.keep_h})
             optkey = (optkey ^ v) * 1099511628211LL;
         if (!P.graph_exec || P.graph_tol != c.tol || P.graph_ntol != c.ntol || P.graph_dbg != c.dbg || P.graph_gen != P.sched_gen ||
             P.graph_opt != optkey) {
@@ -1969,6 +2027,10 @@ int stmmqr_plan_set_groups(stmmqr_plan *plan, const int *group)
 {
     if (!plan || !group) return fail(STMMQR_ERR_INVALID, "null plan / groups");
     stmmqr_plan &P = *plan;
+    if (!P.keep_h)                                           // (the plan's own rebuilds pass group 0 for every front)
+        for (long f = 0; f < P.nf; f++)
+            if (group[f] != 0)
+                return fail(STMMQR_ERR_INVALID, "a plan without H (keepH = 0) takes one group only: no sharded R-only factorization");
     HIPCHK(hipSetDevice(P.device));
     // validate BEFORE anything of the plan changes: a refused call leaves groups and schedule as they were
     auto gid = [&](long f) { return group[f] < 0 ? -1 : (group[f] & ~STMMQR_GROUP_SHARED); };
@@ -2077,7 +2139,9 @@ int stmmqr_plan_download(stmmqr_plan *plan, double *Stack, stm_long *Rblock_off,
             const long long w1 = std::min(P.rh_total, w0 + win);
             double *out = P.d_bounce.p + (i & 1) * win;
             if (i >= 2 && hipEventSynchronize(evw[i & 1]) != hipSuccess) rc = 1;       // (the copy that last read this half is done)
-            if (!rc && stm_launch_rh_window(c, P.d_lists.p + P.own_off, P.n_own, parts, P.d_fin.p, P.d_kept.p, P.d_RH.p, w0, w1, out, st)) rc = 1;
+            if (!rc && (P.keep_h ? stm_launch_rh_window(c, P.d_lists.p + P.own_off, P.n_own, parts, P.d_fin.p, P.d_kept.p, P.d_RH.p, w0, w1, out, st)
+                                 : stm_launch_r_window(c, P.d_lists.p + P.own_off, P.n_own, parts, P.d_fin.p, P.d_kept.p, P.d_RH.p, w0, w1, out, st)))
+                rc = 1;
             if (!rc && hipMemcpyAsync(Stack + w0, out, (size_t)(w1 - w0) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) rc = 1;
             if (!rc && hipEventRecord(evw[i & 1], st) != hipSuccess) rc = 1;
         }
@@ -2119,6 +2183,7 @@ int stmmqr_plan_download(stmmqr_plan *plan, double *Stack, stm_long *Rblock_off,
         maxfm = std::max(maxfm, (long)nm.fm);
         rank += nm.rank;
     }
+    if (!P.keep_h) { Hii = nullptr; HPinv = nullptr; }        // (R only: no qr_hpinv, SparseQR_factorize.c:717)
     if (!all_here) {
         // sharded run: the caller merges the shards and runs qr_hpinv on the union; Hii stays in S-row ids
         if (Hii)

@@ -103,6 +103,20 @@ int stm_launch_rh_window(const DevCtx &c, const int *flist, int nfr, int maxpart
                          long long w0, long long w1, double *out, hipStream_t st);
 int stm_launch_rh_copy(const DevCtx &c, const int *flist, const int *nparts, int nfr, int maxparts, double *RH,
                        hipStream_t st);
+// factors without H (keepH = 0: qr_rhpack's R-only layout) and products with A (stmmqr_qless.hip); the block offsets come from
+// stm_launch_rh_scan as for R+H
+int stm_launch_r_count(const DevCtx &c, const int *flist, int nfr, hipStream_t st);
+int stm_launch_r_copy(const DevCtx &c, const int *flist, const int *nparts, int nfr, int maxparts, double *RH, hipStream_t st);
+int stm_launch_r_window(const DevCtx &c, const int *flist, int nfr, int maxparts, const long long *fin, const char *kept, const double *RH,
+                        long long w0, long long w1, double *out, hipStream_t st);
+int stm_launch_rh_zero(const DevCtx &c, const FrontSym *cs, const int *flist, int nfr, int maxparts, const char *kept, double *scratch,
+                       hipStream_t st);
+int stm_launch_r_unpack(const DevCtx &c, const int *flist, int nfr, int maxparts, const char *kept, const double *RH, const FrontSym *cs,
+                        double *scratch, hipStream_t st);
+int stm_launch_spmv(int rows, const int *ptr, const int *idx, const int *vpos, const double *Ax, const double *X, long long ldx,
+                    const double *B, long long ldb, double *Y, long long ldy, long long nrhs, hipStream_t st);
+int stm_launch_colnorm2(long long rows, const double *X, long long ldx, int ncols, double *out, hipStream_t st);
+int stm_launch_add_cols(int rows, int ncols, const double *D, long long ldd, double *X, long long ldx, hipStream_t st);
 // Q-apply / triangular solve on the resident factors
 // Several right-hand sides per launch (QR_qmult / QR_solve take blocks of them: qr_panel, SparseQR.c:1591-1706): every kernel of
 // these operations takes right-hand side blockIdx.y (or .z) of a BATCH -- the same workgroups, one set per vector, in the same

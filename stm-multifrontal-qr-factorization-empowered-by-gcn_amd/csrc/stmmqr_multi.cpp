@@ -349,6 +349,7 @@ static int shared_front_loop(stmmqr_plan *plan, int group, stm_long f, int first
 
 int stmmqr_factorize_shared_front(stmmqr_plan *plan, int group, stm_long f, int first_rank, int nranks, const stmmqr_transport *tr)
 {
+    if (plan && !plan->keep_h) return fail(STMMQR_ERR_INVALID, "a plan without H (keepH = 0) has no shared fronts");
     return shared_front_loop(plan, group, f, first_rank, nranks, tr, true);
 }
 
@@ -373,6 +374,7 @@ int stmmqr_factorize_exchange(stmmqr_plan *plan, stm_long nout, const stm_long *
                               const stm_long *in_front, const int *in_peer, const stmmqr_transport *tr)
 {
     if (!plan || !plan->begun) return fail(STMMQR_ERR_INVALID, "stmmqr_factorize_begin was not called");
+    if (!plan->keep_h) return fail(STMMQR_ERR_INVALID, "a plan without H (keepH = 0) takes one group only: no subtree exchange");
     if (!tr || !tr->send || !tr->recv) return fail(STMMQR_ERR_INVALID, "null transport");
     if (nout < 0 || nin < 0 || (nout > 0 && (!out_front || !out_peer)) || (nin > 0 && (!in_front || !in_peer)))
         return fail(STMMQR_ERR_INVALID, "stmmqr_factorize_exchange: null lists");
@@ -459,6 +461,7 @@ static long long front_cols_bound(const stmmqr_plan &P, stm_long f, int part, in
 int stmmqr_shared_front_gather(stmmqr_plan *plan, stm_long f, int first_rank, int nranks, const stmmqr_transport *tr)
 {
     if (!plan || !plan->begun) return fail(STMMQR_ERR_INVALID, "stmmqr_factorize_begin was not called");
+    if (!plan->keep_h) return fail(STMMQR_ERR_INVALID, "a plan without H (keepH = 0) has no shared fronts");
     if (!tr || !tr->send || !tr->recv) return fail(STMMQR_ERR_INVALID, "null transport");
     stmmqr_plan &P = *plan;
     if (f < 0 || f >= P.nf || (size_t)f >= P.shared.size() || !P.shared[(size_t)f]) return fail(STMMQR_ERR_INVALID, "not a shared front");
@@ -508,6 +511,7 @@ int stmmqr_shared_front_gather(stmmqr_plan *plan, stm_long f, int first_rank, in
 int stmmqr_factorize_phases(stmmqr_plan *plan, const stmmqr_shard_phases *ph, const stmmqr_transport *tr)
 {
     if (!plan || !plan->begun) return fail(STMMQR_ERR_INVALID, "stmmqr_factorize_begin was not called");
+    if (!plan->keep_h) return fail(STMMQR_ERR_INVALID, "a plan without H (keepH = 0) takes one group only: no phases");
     if (!ph || ph->nphase < 1 || !ph->out_ptr || !ph->in_ptr || !ph->shared_front || !ph->has_group)
         return fail(STMMQR_ERR_INVALID, "stmmqr_factorize_phases: null phase lists");
     if (!tr) return fail(STMMQR_ERR_INVALID, "null transport");

@@ -326,6 +326,14 @@ int stm_launch_rh_unpack(const DevCtx &c, const FrontSym *cs, const int *flist, 
     hipLaunchKernelGGL(k_rh_unpack, dim3(maxparts, nfr), dim3(NT), 0, st, c, cs, flist, kept, RH, scratch, 1);
     return (int)hipGetLastError();
 }
+// the zero fill alone (phase 0): the R-only scatter (stm_launch_r_unpack) writes fewer rows than it clears
+int stm_launch_rh_zero(const DevCtx &c, const FrontSym *cs, const int *flist, int nfr, int maxparts, const char *kept, double *scratch,
+                       hipStream_t st)
+{
+    if (nfr <= 0) return 0;
+    hipLaunchKernelGGL(k_rh_unpack, dim3(maxparts, nfr), dim3(NT), 0, st, c, cs, flist, kept, nullptr, scratch, 0);
+    return (int)hipGetLastError();
+}
 int stm_launch_rh_window(const DevCtx &c, const int *flist, int nfr, int maxparts, const long long *fin, const char *kept, const double *RH,
                          long long w0, long long w1, double *out, hipStream_t st)
 {

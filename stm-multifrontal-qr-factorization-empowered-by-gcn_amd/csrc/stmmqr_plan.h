@@ -128,6 +128,8 @@ struct stmmqr_plan {
     size_t evused = 0;
     long m = 0, n = 0, anz = 0, nf = 0, maxfn = 0, rjsize = 0, hisize = 0;
     int do_rank = 1;
+    int keep_h = 1;                                    // QRsym->keepH: 0 = the packed blocks hold R only (qr_rhpack's keepH = 0 layout);
+                                                       //  no Q-apply, one group only (stmmqr_plan_set_groups refuses)
     int ca_min = STM_CA_MIN_ROWS;                      // (env STMMQR_CA_MIN at plan time: experiments)
     int plan_algo = 0;                                 // g_opt.panel_algo when the schedule was built
     int tall_min = STM_TALL_MIN;                       // g_opt.tall_min_rows when the schedule was built
@@ -160,6 +162,7 @@ struct stmmqr_plan {
     std::vector<int> f_t0, f_t1, c_t1;   // slab: [f_t0, f_t1]; contribution block: [f_t1, c_t1]  (steps of group 0)
     long long rh_cap = 0;                // capacity of the R+H arena (doubles)
     long long rh_est_total = 0;          // all packed R+H blocks if no pivot column dies (symbolic; exact for full-rank input)
+    std::vector<long long> rh_est_front; // ... per front (keepH = 0: the arena holds those of the fronts that do not keep their slab)
     int rh_grow = 0;                     // 0: the arena is sized from that estimate; 1: from the hard bounds (it overflowed once)
     double rh_est_scale = 1.0;           // ... times STMMQR_RH_EST_SCALE, read once when the plan is created (tests shrink the estimate)
     long long scr_doubles = 0;           // scratch of the resident-factor operations: the widest tree level in front form
@@ -207,6 +210,12 @@ struct stmmqr_plan {
     DevBuf<unsigned long long> d_dbg, d_amax;
     DevBuf<double> d_sig;                           // {sg, 1/sg}: magnitude guard of the panel kernels
     DevBuf<char> d_Rdead;
+    // products with A on the device (stmmqr_plan_spmv, the seminormal solve): A's column form and a row form whose entries point
+    // at A's values (d_Ax), built at the first such call after set_pattern (stm_ensure_a_index)
+    DevBuf<int> d_Acp, d_Aci, d_Arp, d_Arj, d_Arq;
+    std::vector<int> h_smap;                    // host copy of d_smap (what those forms are built from)
+    bool a_index_ready = false;
+    DevBuf<double> d_csB, d_csX, d_csR, d_csZ, d_csY, d_csD, d_csN;   // the seminormal solve's vectors (grown on demand)
 
     // results of the last factorization
     bool factored = false, begun = false, first_group = true;
@@ -264,6 +273,7 @@ struct stmmqr_plan {
         add(d_Stair); add(d_Hii); add(d_Cmap); add(d_Cursor); add(d_lists); add(d_smap); add(d_Rhoff); add(d_wlists);
         add(d_wcnt); add(d_wcnt2); add(d_wflag); add(d_wflag2); add(d_Rboff); add(d_Rdead); add(d_Ypend); add(d_ypoff);
         add(d_rhtop); add(d_fin); add(d_kept); add(d_scr); add(d_bounce); add(d_fs_scr);
+        add(d_Acp); add(d_Aci); add(d_Arp); add(d_Arj); add(d_Arq);
         return b;
     }
     DevCtx ctx() const
@@ -307,4 +317,5 @@ struct StepReq { int step, what, cb_first, cb_stride, cb_count; };
 // planner / scheduler entry points used by the other host translation units (stmmqr_host.cpp)
 int stm_run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req);
 int stm_ensure_device(int device);
+int stm_ensure_a_index(stmmqr_plan &P);
 extern "C" int stm_check_c_slot(const stmmqr_plan &P, stm_long f, long long csize, const char *what);     // (defined inside the C ABI block)

@@ -208,6 +208,12 @@ DevCtx res_ctx(stmmqr_plan &P)
     if (P.recycle) { c.fs = P.d_fs_scr.p; c.Farena = P.d_scr.p; }
     return c;
 }
+// staged blocks back in front form: R+H by k_rh_unpack, R only (keepH = 0) by k_rh_unpack's zero fill + k_r_unpack
+int unpack_fronts(stmmqr_plan &P, const DevCtx &c, const int *flist, int nfr)
+{
+    if (P.keep_h) return stm_launch_rh_unpack(c, P.d_fs_scr.p, flist, nfr, 64, P.d_kept.p, P.d_RH.p, P.d_scr.p, P.stream);
+    return stm_launch_r_unpack(c, flist, nfr, 64, P.d_kept.p, P.d_RH.p, P.d_fs_scr.p, P.d_scr.p, P.stream);
+}
 int level_to_front_form(stmmqr_plan &P, size_t l)
 {
     if (!P.recycle) return 0;
@@ -216,12 +222,12 @@ int level_to_front_form(stmmqr_plan &P, size_t l)
     if (P.scr_all) {
         if (P.scr_valid) return 0;
         // every front at once, kept until the next factorization (marked valid only once the launch was accepted)
-        const int e = stm_launch_rh_unpack(c, P.d_fs_scr.p, P.d_lists.p + P.own_off, P.n_own, 64, P.d_kept.p, P.d_RH.p, P.d_scr.p, P.stream);
+        const int e = unpack_fronts(P, c, P.d_lists.p + P.own_off, P.n_own);
         P.scr_valid = (e == 0);
         return e;
     }
     if (LV[l].n_all <= 0) return 0;
-    return stm_launch_rh_unpack(c, P.d_fs_scr.p, P.d_lists.p + LV[l].all_off, LV[l].n_all, 64, P.d_kept.p, P.d_RH.p, P.d_scr.p, P.stream);
+    return unpack_fronts(P, c, P.d_lists.p + LV[l].all_off, LV[l].n_all);
 }
 
 // the per-vector buffers of the resident-factor operations for a batch of nb right-hand sides (grown on demand, never shrunk)
@@ -384,6 +390,7 @@ int stmmqr_plan_qmult(stmmqr_plan *plan, int method, double *X, stm_long ldx, st
     if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
     if (!X || k < 0 || method < 0 || method > 3 || ldx < ((method <= 1) ? plan->m : k))
         return fail(STMMQR_ERR_INVALID, "bad qmult arguments");
+    if (!plan->keep_h) return fail(STMMQR_ERR_INVALID, "the plan keeps no Householder vectors (keepH = 0): no Q-apply");
     stmmqr_plan &P = *plan;
     HIPCHK(hipSetDevice(P.device));
     LCHK(ensure_rowmap(P));
@@ -480,6 +487,8 @@ int stmmqr_plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *
 {
     if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
     if (!B || !X || ldb < plan->m || ldx < plan->n || nrhs < 0) return fail(STMMQR_ERR_INVALID, "bad solve arguments");
+    if (!plan->keep_h)
+        return fail(STMMQR_ERR_INVALID, "the plan keeps no Householder vectors (keepH = 0): no Q'B; stmmqr_plan_solve_seminormal solves with R only");
     stmmqr_plan &P = *plan;
     HIPCHK(hipSetDevice(P.device));
     LCHK(ensure_rowmap(P));
@@ -499,6 +508,278 @@ int stmmqr_plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *
     }
     LCHK(download_cols(P, P.d_Yall, X, ldx, n, nrhs));
     return check_device_err(P, "internal: live pivot count of a front differs from its rank");
+}
+
+// ---- products with A and the corrected seminormal equations (factors with or without H) ----
+namespace {
+// nb vectors Z (device, stride n) -> Y (device, stride m) = R' \ (E' Z): the launches of stmmqr_plan_rsolve's system 3
+int rt_vectors(stmmqr_plan &P, const double *Z, double *Y, int nb)
+{
+    hipStream_t st = P.stream;
+    const long m = P.m, n = P.n;
+    LCHK(ensure_rhs_batch(P, nb));
+    const RhsBatch RB = rhs_strides(P);
+    DevCtx c = res_ctx(P);
+    const int *L0 = P.d_lists.p;
+    const auto &LV = P.glevels[0];
+    LCHK(stm_launch_perm(Z, P.has_qfill ? P.d_Qfill.p : nullptr, P.d_Xs.p, (int)n, 0, st, nb, n, n));
+    HIPCHK(hipMemsetAsync(P.d_Xr.p, 0, (size_t)nb * (size_t)std::max(1L, m) * sizeof(double), st));
+    for (size_t l = 0; l < LV.size(); l++) {
+        LCHK(level_to_front_form(P, l));
+        LCHK(stm_launch_rtsolve(c, L0 + LV[l].all_off, LV[l].n_all, P.d_Xs.p, P.d_U.p, P.d_Xr.p, P.d_rowbase.p, P.level_lds_rt[l], st, nb, RB));
+    }
+    HIPCHK(hipMemcpyAsync(Y, P.d_Xr.p, (size_t)nb * (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+// nb vectors Y (device, stride m, R's row order) -> X (device, stride n) = E (R \ Y): stmmqr_plan_rsolve's system 1
+int r_vectors(stmmqr_plan &P, const double *Y, double *X, int nb)
+{
+    hipStream_t st = P.stream;
+    const long m = P.m, n = P.n;
+    LCHK(ensure_rhs_batch(P, nb));
+    LCHK(stm_launch_perm(Y, P.d_Wmap.p, P.d_W.p, (int)m, 0, st, nb, m, m));
+    LCHK(rsolve_vector(P, nb));
+    LCHK(stm_launch_perm(P.d_Xs.p, P.has_qfill ? P.d_Qfill.p : nullptr, X, (int)n, 1, st, nb, n, n));
+    return 0;
+}
+// Y = A X (trans 0: X n x nrhs, Y m x nrhs), A' X (trans 1: X m, Y n), or with B (trans 0 only) Y = B - A X; device arrays
+int spmv_dev(stmmqr_plan &P, int trans, const double *X, long long ldx, const double *B, long long ldb, double *Y, long long ldy, long long nrhs)
+{
+    if (trans) return stm_launch_spmv((int)P.n, P.d_Acp.p, P.d_Aci.p, nullptr, P.d_Ax.p, X, ldx, B, ldb, Y, ldy, nrhs, P.stream);
+    return stm_launch_spmv((int)P.m, P.d_Arp.p, P.d_Arj.p, P.d_Arq.p, P.d_Ax.p, X, ldx, B, ldb, Y, ldy, nrhs, P.stream);
+}
+int grow(DevBuf<double> &d, size_t n) { return (d.p && d.n >= n) ? 0 : d.alloc(std::max<size_t>(n, 1)); }
+}  // namespace
+
+// Y = A X (trans 0) or A' X (trans 1) with the values of the last factorization; see include/stmmqr_hip.h
+int stmmqr_plan_spmv(stmmqr_plan *plan, int trans, const double *X, stm_long ldx, double *Y, stm_long ldy, stm_long nrhs, int on_device)
+{
+    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    stmmqr_plan &P = *plan;
+    const long xr = trans ? P.m : P.n, yr = trans ? P.n : P.m;
+    if (!X || !Y || nrhs < 0 || (trans != 0 && trans != 1) || ldx < xr || ldy < yr) return fail(STMMQR_ERR_INVALID, "bad spmv arguments");
+    if (!P.pattern_set) return fail(STMMQR_ERR_INVALID, "pattern of A was never given");
+    HIPCHK(hipSetDevice(P.device));
+    if (nrhs == 0 || yr == 0) return 0;
+    LCHK(stm_ensure_a_index(P));
+    if (on_device) {
+        LCHK(spmv_dev(P, trans, X, ldx, nullptr, 0, Y, ldy, nrhs));
+        HIPCHK(hipStreamSynchronize(P.stream));
+        return 0;
+    }
+    LCHK(grow(P.d_csX, (size_t)xr * (size_t)nrhs));
+    LCHK(grow(P.d_csY, (size_t)yr * (size_t)nrhs));
+    LCHK(upload_cols(P, P.d_csX, X, ldx, xr, nrhs));
+    LCHK(spmv_dev(P, trans, P.d_csX.p, xr, nullptr, 0, P.d_csY.p, yr, nrhs));
+    return download_cols(P, P.d_csY, Y, ldy, yr, nrhs);
+}
+
+// Least squares through the corrected seminormal equations with R only; see include/stmmqr_hip.h
+int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int refine,
+                                 int on_device, double *info)
+{
+    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    stmmqr_plan &P = *plan;
+    const long m = P.m, n = P.n;
+    if (!B || !X || nrhs < 0 || refine < 0 || ldb < m || ldx < n) return fail(STMMQR_ERR_INVALID, "bad seminormal solve arguments");
+    if (!P.pattern_set) return fail(STMMQR_ERR_INVALID, "pattern of A was never given");
+    HIPCHK(hipSetDevice(P.device));
+    LCHK(ensure_rowmap(P));                          // (fills level_lds_rt on the first resident-factor call of the plan)
+    for (int need : P.level_lds_rt)                  // (the R' \ step: before any launch of the solve)
+        if (need > 131072) return fail(STMMQR_ERR_TOO_LARGE, "a front is too wide for the one-workgroup R' solve");
+    LCHK(stm_ensure_a_index(P));
+    if (info) *info = 0;
+    if (nrhs == 0) return 0;
+    hipStream_t st = P.stream;
+    if (!P.d_U.p) {
+        LCHK(P.d_U.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, P.rjsize)));
+        LCHK(P.d_Xr.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, m)));
+    }
+    const int nbmax = rhs_batch_max();
+    const size_t mm = (size_t)std::max(1L, m), nn = (size_t)std::max(1L, n), nbm = (size_t)std::min<stm_long>(nbmax, nrhs);
+    LCHK(grow(P.d_csB, mm * (size_t)nrhs));
+    LCHK(grow(P.d_csX, nn * (size_t)nrhs));
+    LCHK(grow(P.d_csR, mm * nbm)); LCHK(grow(P.d_csY, mm * nbm));
+    LCHK(grow(P.d_csZ, nn * nbm)); LCHK(grow(P.d_csD, nn * nbm));
+    LCHK(grow(P.d_csN, 3 * (size_t)nrhs + 1));
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
+    if (on_device) {
+        for (stm_long j = 0; j < nrhs; j++)
+            HIPCHK(hipMemcpyAsync(P.d_csB.p + j * m, B + j * ldb, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
+    } else LCHK(upload_cols(P, P.d_csB, B, ldb, m, nrhs));
+    for (stm_long j = 0; j < nrhs; j += nbmax) {
+        const int nb = (int)std::min<stm_long>(nbmax, nrhs - j);
+        const double *b = P.d_csB.p + j * m;
+        double *x = P.d_csX.p + j * n;
+        LCHK(spmv_dev(P, 1, b, m, nullptr, 0, P.d_csZ.p, n, nb));                        // z = A'b
+        LCHK(rt_vectors(P, P.d_csZ.p, P.d_csY.p, nb));                                    // y = R' \ (E'z)
+        LCHK(r_vectors(P, P.d_csY.p, x, nb));                                             // x = E (R \ y)
+        for (int it = 0; it < refine; it++) {
+            LCHK(spmv_dev(P, 0, x, n, b, m, P.d_csR.p, m, nb));                          // r = b - A x
+            LCHK(spmv_dev(P, 1, P.d_csR.p, m, nullptr, 0, P.d_csZ.p, n, nb));             // A'r
+            LCHK(rt_vectors(P, P.d_csZ.p, P.d_csY.p, nb));
+            LCHK(r_vectors(P, P.d_csY.p, P.d_csD.p, nb));
+            LCHK(stm_launch_add_cols((int)n, nb, P.d_csD.p, n, x, n, st));                // x += E R^-1 R^-T E' A'r
+        }
+        if (info) {
+            LCHK(spmv_dev(P, 0, x, n, b, m, P.d_csR.p, m, nb));
+            LCHK(spmv_dev(P, 1, P.d_csR.p, m, nullptr, 0, P.d_csZ.p, n, nb));
+            LCHK(stm_launch_colnorm2(n, P.d_csZ.p, n, nb, P.d_csN.p + j, st));           // |A'r|^2, |x|^2, |b|^2
+            LCHK(stm_launch_colnorm2(n, x, n, nb, P.d_csN.p + nrhs + j, st));
+            LCHK(stm_launch_colnorm2(m, b, m, nb, P.d_csN.p + 2 * nrhs + j, st));
+        }
+    }
+    if (info) {
+        LCHK(stm_launch_colnorm2(P.anz, P.d_Ax.p, std::max(1L, P.anz), 1, P.d_csN.p + 3 * nrhs, st));   // |A|_F^2
+        std::vector<double> nr((size_t)(3 * nrhs + 1));
+        HIPCHK(hipMemcpyAsync(nr.data(), P.d_csN.p, nr.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const double af = std::sqrt(nr[(size_t)(3 * nrhs)]);
+        double worst = 0;
+        for (stm_long j = 0; j < nrhs; j++) {
+            const double den = af * (af * std::sqrt(nr[(size_t)(nrhs + j)]) + std::sqrt(nr[(size_t)(2 * nrhs + j)]));
+            const double q = std::sqrt(nr[(size_t)j]);
+            const double v = den > 0 ? q / den : (q > 0 ? INFINITY : 0.0);
+            worst = std::max(worst, v);
+        }
+        *info = worst;
+    }
+    if (on_device) {
+        for (stm_long j = 0; j < nrhs; j++)
+            HIPCHK(hipMemcpyAsync(X + j * ldx, P.d_csX.p + j * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+    } else LCHK(download_cols(P, P.d_csX, X, ldx, n, nrhs));
+    return check_device_err(P, "internal: live pivot count of a front differs from its rank");
+}
+
+int stmmqr_plan_keep_h(const stmmqr_plan *plan) { return plan ? plan->keep_h : -1; }
+
+// ---- a caller's matrix on the device (the sparseqr-level seminormal solve: products with the FULL A, singletons included) ----
+struct stm_aop {
+    int device = 0;
+    hipStream_t st = nullptr;
+    long m = 0, n = 0;
+    DevBuf<int> cp, ci, rp, rj, rq;
+    DevBuf<double> ax, X, B, Y;
+    ~stm_aop() { if (st) (void)hipStreamDestroy(st); }
+};
+int stm_aop_create(int device, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax, stm_aop **out)
+{
+    if (!out || !Ap || (Ap[n] > 0 && (!Ai || !Ax)) || m < 0 || n < 0) return fail(STMMQR_ERR_INVALID, "bad matrix");
+    *out = nullptr;
+    const long anz = Ap[n];
+    if (m >= (1L << 30) || n >= (1L << 30) || anz >= (1L << 31) - 1) return fail(STMMQR_ERR_TOO_LARGE, "matrix exceeds the 32-bit device index range");
+    int e = stm_ensure_device(device);
+    if (e) return e;
+    std::unique_ptr<stm_aop> op(new (std::nothrow) stm_aop());
+    if (!op) return fail(STMMQR_ERR_OUT_OF_MEMORY, "host allocation failed");
+    (void)hipGetDevice(&op->device);
+    HIPCHK(hipStreamCreateWithFlags(&op->st, hipStreamNonBlocking));
+    op->m = m; op->n = n;
+    std::vector<int> acp((size_t)n + 1), aci((size_t)std::max(1L, anz)), arp((size_t)m + 1, 0), arj((size_t)std::max(1L, anz)),
+        arq((size_t)std::max(1L, anz));
+    for (long j = 0; j <= n; j++) acp[(size_t)j] = (int)Ap[j];
+    for (long p = 0; p < anz; p++) {
+        if (Ai[p] < 0 || Ai[p] >= m) return fail(STMMQR_ERR_INVALID, "row index out of range");
+        aci[(size_t)p] = (int)Ai[p]; arp[(size_t)Ai[p] + 1]++;
+    }
+    for (long i = 0; i < m; i++) arp[(size_t)i + 1] += arp[(size_t)i];
+    std::vector<int> next(arp.begin(), arp.end() - 1);
+    for (long j = 0; j < n; j++)
+        for (long p = Ap[j]; p < Ap[j + 1]; p++) { const int q = next[(size_t)Ai[p]]++; arj[(size_t)q] = (int)j; arq[(size_t)q] = (int)p; }
+    std::vector<double> ax(Ax, Ax + anz);
+    if (ax.empty()) ax.push_back(0.0);
+    LCHK(op->cp.upload(acp, op->st)); LCHK(op->ci.upload(aci, op->st)); LCHK(op->rp.upload(arp, op->st));
+    LCHK(op->rj.upload(arj, op->st)); LCHK(op->rq.upload(arq, op->st)); LCHK(op->ax.upload(ax, op->st));
+    HIPCHK(hipStreamSynchronize(op->st));
+    *out = op.release();
+    return 0;
+}
+void stm_aop_destroy(stm_aop *op) { delete op; }
+int stm_aop_apply(stm_aop *op, int trans, const double *X, stm_long ldx, const double *B, stm_long ldb, double *Y, stm_long ldy,
+                  stm_long nrhs)
+{
+    if (!op) return fail(STMMQR_ERR_INVALID, "null operator");
+    const long xr = trans ? op->m : op->n, yr = trans ? op->n : op->m;
+    if (nrhs <= 0 || yr == 0) return 0;
+    HIPCHK(hipSetDevice(op->device));
+    auto up = [&](DevBuf<double> &d, const double *H, long ld, long rows) -> int {
+        if (d.n < (size_t)(rows * nrhs) || !d.p) LCHK(d.alloc((size_t)std::max(1L, rows * nrhs)));
+        if (rows > 0)
+            HIPCHK(hipMemcpy2DAsync(d.p, (size_t)rows * sizeof(double), H, (size_t)ld * sizeof(double), (size_t)rows * sizeof(double),
+                                    (size_t)nrhs, hipMemcpyHostToDevice, op->st));
+        return 0;
+    };
+    LCHK(up(op->X, X, ldx, xr));
+    if (B) LCHK(up(op->B, B, ldb, yr));
+    if (op->Y.n < (size_t)(yr * nrhs) || !op->Y.p) LCHK(op->Y.alloc((size_t)(yr * nrhs)));
+    if (trans) LCHK(stm_launch_spmv((int)op->n, op->cp.p, op->ci.p, nullptr, op->ax.p, op->X.p, xr, nullptr, 0, op->Y.p, yr, nrhs, op->st));
+    else LCHK(stm_launch_spmv((int)op->m, op->rp.p, op->rj.p, op->rq.p, op->ax.p, op->X.p, xr, B ? op->B.p : nullptr, yr, op->Y.p, yr, nrhs, op->st));
+    HIPCHK(hipMemcpy2DAsync(Y, (size_t)ldy * sizeof(double), op->Y.p, (size_t)yr * sizeof(double), (size_t)yr * sizeof(double), (size_t)nrhs,
+                            hipMemcpyDeviceToHost, op->st));
+    HIPCHK(hipStreamSynchronize(op->st));
+    return 0;
+}
+
+// Least squares by the corrected seminormal equations on a SparseQR object (with or without H): x = E R^-1 R^-T E' A'b, then
+// `refine` times r = b - A x, x += E R^-1 R^-T E' A'r.  A' and A are the caller's full matrix (singleton rows and columns
+// included) on the device (stm_aop); R'\ and R\ are systems 3 and 1 of stmmqr_sparseqr_solve (singleton rows + the plan).
+// info: max over the columns of |A'r| / (|A|_F (|A|_F |x| + |b|)).
+int stmmqr_sparseqr_solve_seminormal(stmmqr_qr *qr, const stm_long *Ap, const stm_long *Ai, const double *Ax, const double *B, stm_long ldb,
+                                     stm_long nrhs, double *X, stm_long ldx, int refine, double *info)
+{
+    stm_long m = 0, n = 0;
+    if (!qr || stm_sparseqr_dims(qr, &m, &n) || !Ap || !B || !X || nrhs < 0 || refine < 0)
+        return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_solve_seminormal: bad arguments");
+    if (ldb < m || ldx < n) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_solve_seminormal: bad leading dimension");
+    if (Ap[n] < 0) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_solve_seminormal: bad matrix");
+    if (info) *info = 0;
+    if (nrhs == 0) return 0;
+    stm_aop *op = nullptr;
+    int e = stm_aop_create(-1, m, n, Ap, Ai, Ax, &op);
+    if (e) return e;
+    try {
+        const size_t M = (size_t)std::max<stm_long>(m, 1), N = (size_t)std::max<stm_long>(n, 1), K = (size_t)nrhs;
+        std::vector<double> z(N * K), y(M * K), r(M * K), d(N * K);
+        // x = E R^-1 R^-T E' z for z (n x nrhs): out (n x nrhs, leading dimension ld)
+        auto rr = [&](double *out, stm_long ld) -> int {
+            int e2 = stmmqr_sparseqr_solve(qr, 3, z.data(), (stm_long)N, nrhs, y.data(), (stm_long)M);
+            if (!e2) e2 = stmmqr_sparseqr_solve(qr, 1, y.data(), (stm_long)M, nrhs, out, ld);
+            return e2;
+        };
+        e = stm_aop_apply(op, 1, B, ldb, nullptr, 0, z.data(), (stm_long)N, nrhs);                 // z = A'b
+        if (!e) e = rr(X, ldx);
+        for (int it = 0; it < refine && !e; it++) {
+            e = stm_aop_apply(op, 0, X, ldx, B, ldb, r.data(), (stm_long)M, nrhs);                 // r = b - A x
+            if (!e) e = stm_aop_apply(op, 1, r.data(), (stm_long)M, nullptr, 0, z.data(), (stm_long)N, nrhs);
+            if (!e) e = rr(d.data(), (stm_long)N);
+            if (!e)
+                for (stm_long j = 0; j < nrhs; j++)
+                    for (stm_long k = 0; k < n; k++) X[k + j * ldx] += d[(size_t)k + (size_t)j * N];
+        }
+        if (!e && info) {
+            e = stm_aop_apply(op, 0, X, ldx, B, ldb, r.data(), (stm_long)M, nrhs);
+            if (!e) e = stm_aop_apply(op, 1, r.data(), (stm_long)M, nullptr, 0, z.data(), (stm_long)N, nrhs);
+            if (!e) {
+                double af = 0;
+                for (stm_long p = 0; p < Ap[n]; p++) af += Ax[p] * Ax[p];
+                af = std::sqrt(af);
+                double worst = 0;
+                for (stm_long j = 0; j < nrhs; j++) {
+                    double zz = 0, xx = 0, bb = 0;
+                    for (stm_long k = 0; k < n; k++) { zz += z[(size_t)k + (size_t)j * N] * z[(size_t)k + (size_t)j * N]; xx += X[k + j * ldx] * X[k + j * ldx]; }
+                    for (stm_long i = 0; i < m; i++) bb += B[i + j * ldb] * B[i + j * ldb];
+                    const double den = af * (af * std::sqrt(xx) + std::sqrt(bb)), q = std::sqrt(zz);
+                    worst = std::max(worst, den > 0 ? q / den : (q > 0 ? INFINITY : 0.0));
+                }
+                *info = worst;
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        e = stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_sparseqr_solve_seminormal: out of memory");
+    }
+    stm_aop_destroy(op);
+    return e;
 }
 
 }  // extern "C"

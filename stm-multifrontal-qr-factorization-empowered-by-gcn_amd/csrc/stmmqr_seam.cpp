@@ -229,7 +229,7 @@ stm_qr_numeric *qr_factorize(stm_sparse_csc **Ahandle, stm_long freeA, double to
     v.hisize = S->hisize; v.do_rank_detection = S->do_rank_detection;
     v.Sp = S->Sp; v.Sj = S->Sj; v.Qfill = S->Qfill; v.PLinv = S->PLinv; v.Sleft = S->Sleft;
     v.Child = S->Child; v.Childp = S->Childp; v.Super = S->Super; v.Rp = S->Rp; v.Rj = S->Rj; v.Post = S->Post;
-    v.Hip = S->Hip; v.Fm = S->Fm; v.maxstack = S->maxstack;
+    v.Hip = S->Hip; v.Fm = S->Fm; v.maxstack = S->maxstack; v.r_only = S->keepH ? 0 : 1;
 
     int st = 0;
     // the plan: from the cache when an equal qr_symbolic was factorized before (same options), else built now
@@ -347,6 +347,8 @@ stm_qr_numeric *qr_factorize(stm_sparse_csc **Ahandle, stm_long freeA, double to
     const double t_alloc = now_ms();
     const double P_rh_bytes = 8.0 * (double)P->rh_total;
     if (ok) {
+        // (keepH = 0: the download leaves Hii and HPinv alone -- no qr_hpinv, SparseQR_factorize.c:717 -- their contents are
+        //  undefined, as the reference's)
         st = stmmqr_plan_download(P, N->Stacks[0], roff.data(), N->Rdead, N->HStair, N->HTau, N->Hii, N->HPinv, N->Hm,
                                   N->Hr, scal, &stats);
         ok = st == 0;
@@ -360,7 +362,7 @@ stm_qr_numeric *qr_factorize(stm_sparse_csc **Ahandle, stm_long freeA, double to
         return nullptr;
     }
     for (stm_long f = 0; f < nf; f++) N->Rblock[f] = N->Stacks[0] + roff[f];
-    N->rank = scal[0]; N->rank1 = scal[1]; N->maxfrank = scal[2]; N->maxfm = scal[3];
+    N->rank = scal[0]; N->rank1 = scal[1]; N->maxfrank = scal[2]; N->maxfm = S->keepH ? scal[3] : -1;   // (qr_hpinv sets maxfm)
     if (cc) cc_dbl(cc, g_layout.SPQR_flopcount) = stats.flops;
     if (timing)
         fprintf(stderr, "[stmmqr_hip] qr_factorize seam: plan %s %.1f ms, factorization %.1f ms (device %.1f), host arrays %.1f ms, "

@@ -371,7 +371,7 @@ stm_long qr_rhpack(int keepH, stm_long m, stm_long n, stm_long npiv, stm_long *S
                    stm_long *p_rm)
 {
     if (m <= 0 || n <= 0) { if (p_rm) *p_rm = 0; return 0; }
-    if (!keepH || !device_ready()) return -1;   // the reference always keeps H (SparseQR_analyze.c:205)
+    if (!device_ready()) return -1;              // (keepH = 0: R only, k_r_count / k_r_copy)
     OneFront X;
     if (!X.init(m, n, npiv, F, m, Stair)) return -1;
     stm_long rm = 0;                            // live pivots (integer input of the copy kernel)
@@ -380,8 +380,9 @@ stm_long qr_rhpack(int keepH, stm_long m, stm_long n, stm_long npiv, stm_long *S
     if (!X.push_num()) return -1;
     std::vector<int> parts(1, 8);
     if (!X.d_parts.up(parts)) return -1;
-    if (stm_launch_rh_count(X.c, X.d_flist.p, 1, nullptr)) return -1;
-    if (stm_launch_rh_copy(X.c, X.d_flist.p, X.d_parts.p, 1, 8, X.d_RH.p, nullptr)) return -1;
+    if (keepH ? stm_launch_rh_count(X.c, X.d_flist.p, 1, nullptr) : stm_launch_r_count(X.c, X.d_flist.p, 1, nullptr)) return -1;
+    if (keepH ? stm_launch_rh_copy(X.c, X.d_flist.p, X.d_parts.p, 1, 8, X.d_RH.p, nullptr)
+              : stm_launch_r_copy(X.c, X.d_flist.p, X.d_parts.p, 1, 8, X.d_RH.p, nullptr)) return -1;
     if (hipDeviceSynchronize() != hipSuccess || !X.pull_num()) return -1;
     std::vector<double> out((size_t)std::max(1LL, X.nm.rsize));
     if (!X.d_RH.down(out.data(), (size_t)X.nm.rsize)) return -1;
@@ -463,7 +464,7 @@ void qr_assemble(stm_long f, stm_long fm, int keepH, stm_long *Super, stm_long *
                  stm_long *Cm, double **Cblock, stm_long *Hr, stm_long *Stair, stm_long *Hii, stm_long *Hip, double *F,
                  stm_long *Cmap)
 {
-    (void)keepH;
+    (void)keepH;                                 // (the reference's qr_assemble does not read it either: Hii is filled for both)
     if (!device_ready()) return;
     const stm_long col1 = Super[f], fp = Super[f + 1] - col1, p1 = Rp[f], fn = Rp[f + 1] - p1;
     const stm_long nch = Childp[f + 1] - Childp[f];

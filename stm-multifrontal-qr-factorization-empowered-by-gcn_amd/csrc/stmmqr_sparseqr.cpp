@@ -93,6 +93,7 @@ struct stmmqr_qr {
     stmmqr_analysis *sym = nullptr;
     stmmqr_plan *plan = nullptr;
     stmmqr_stats stats = {};
+    int keep_h = 1;                                           // stmmqr_sparseqr_set_keep_h: 0 = R only (no Q-apply)
     std::vector<char> Rdead;                                  // of the multifrontal part (n - n1cols)
     double ana_seconds = 0, fac_seconds = 0, sym_info[8] = {};
     const Long *Fp = nullptr, *Fi = nullptr;                  // what the numeric phase factorizes (A or Y)
@@ -319,6 +320,7 @@ static int numeric_impl(stmmqr_qr *QR, int device)
     V.do_rank_detection = S->do_rank_detection;
     V.Sp = S->Sp; V.Sj = S->Sj; V.Qfill = S->Qfill; V.PLinv = S->PLinv; V.Sleft = S->Sleft; V.Child = S->Child; V.Childp = S->Childp;
     V.Super = S->Super; V.Rp = S->Rp; V.Rj = S->Rj; V.Post = S->Post; V.Hip = S->Hip; V.Fm = S->Fm; V.maxstack = S->maxstack;
+    V.r_only = QR->keep_h ? 0 : 1;
     int st = 0;
     QR->plan = stmmqr_plan_create(&V, device, &st);
     if (!QR->plan) return st ? st : STMMQR_ERR_DEVICE;
@@ -332,7 +334,7 @@ static int numeric_impl(stmmqr_qr *QR, int device)
     if (e) return e;
     QR->fac_seconds = wall() - t_fac;
     QR->rank = n1rows + scal[1];                                                            // n1rows + rank1 (SparseQR.c:393)
-    if (n1cols > 0) {
+    if (n1cols > 0 && QR->keep_h) {                                                         // (R only: no HPinv, no Q-apply)
         QR->HP1inv.assign((size_t)std::max<Long>(m, 1), 0);
         for (Long i = 0; i < m; i++) {
             const Long k = QR->P1inv[(size_t)i];
@@ -366,6 +368,22 @@ int stmmqr_sparseqr_symbolic(int ordering, double tol, stm_long m, stm_long n, c
     } catch (...) {
         return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_symbolic: internal error");
     }
+}
+
+int stmmqr_sparseqr_set_keep_h(stmmqr_qr *qr, int keep)
+{
+    if (!qr) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_set_keep_h: null object");
+    if (qr->plan) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_set_keep_h: call it before stmmqr_sparseqr_numeric");
+    qr->keep_h = keep ? 1 : 0;
+    return 0;
+}
+
+// dimensions of the whole problem (stmmqr_sparseqr_solve_seminormal, stmmqr_rfactor.cpp); 0 or STMMQR_ERR_INVALID before numeric
+int stm_sparseqr_dims(const stmmqr_qr *qr, stm_long *m, stm_long *n)
+{
+    if (!qr || !qr->plan) return STMMQR_ERR_INVALID;
+    *m = qr->m; *n = qr->n;
+    return 0;
 }
 
 int stmmqr_sparseqr_numeric(stmmqr_qr *qr, int device)
@@ -410,6 +428,7 @@ int stmmqr_sparseqr_y(const stmmqr_qr *qr, const stm_long **Yp, const stm_long *
 int stmmqr_sparseqr_qmult(stmmqr_qr *qr, int method, const double *X, stm_long ldx, stm_long nrow, stm_long ncol, double *Y, stm_long ldy)
 {
     if (!qr || !X || !Y || method < 0 || method > 3) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_qmult: bad arguments");
+    if (!qr->keep_h) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_qmult: the factorization keeps no Householder vectors (keepH = 0)");
     const Long m = qr->m, n1 = qr->n1rows;
     const bool left = method <= 1;
     if ((left ? nrow : ncol) != m) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_qmult: X does not match the rows of A");
