@@ -392,6 +392,19 @@ int stmmqr_plan_spmv(stmmqr_plan *plan, int trans, const double *X, stm_long ldx
 int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int refine,
                                  int on_device, double *info);
 
+/* Least squares with the right-hand sides carried through the factorization: the plan holds a factorization of the m x (n + nrhs)
+ * matrix [A B] made with ntol = n (the columns of B are never rank-tested), whose Qfill is the identity on the last nrhs columns.
+ * The reflectors reached B as trailing columns, so C = Q'B sits in the last nrhs columns of R and no Q is needed:
+ *   X (n x nrhs, ldx >= n) = E R11^-1 C, C = R(rows of the live columns among the first n, n + j); dead columns among the first n get
+ *   x = 0 (the basic solution, as stmmqr_plan_solve); resid[j] (may be NULL) = the 2-norm of column n + j of R below those rows
+ *   = |b_j - A x_j|_2, 0 where no such rows exist (square full-rank A).
+ * Reads R only: plans with and without H.  No diagonal entry of the B block is a divisor: b = 0 and b in range(A) give finite results.
+ * Batches of STMMQR_RHS_BATCH right-hand sides share one pass over the tree.  on_device: X and resid are device pointers.
+ * STMMQR_ERR_INVALID (the message says why; the plan stays usable): nothing factorized, the last factorization's ntol is not
+ * n = (columns of the plan) - nrhs, or a B column is permuted.  A host that runs the reference's qr_analyze on [A B] and calls
+ * qr_factorize(..., ntol = n) can use it on the seam's cached plan. */
+int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_long ldx, double *resid, int on_device);
+
 /* dense single-front kernels on host buffers (inner seams without the cc argument) */
 stm_long stmmqr_front(stm_long m, stm_long n, stm_long npiv, double tol, stm_long ntol, double *F,
                       stm_long *Stair, char *Rdead, double *Tau, double *flops);
@@ -560,6 +573,31 @@ int stmmqr_plan_export_r(stmmqr_plan *plan, const stm_qr_symbolic *sym, stm_long
                          stm_long *nh, stm_long **Hp, stm_long **Hi, double **Hx, double **HTau);
 int stmmqr_sparselq(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
                     const stmmqr_relax *relax, int device, stmmqr_qr **out);
+
+/* ---- The least-squares object: min |A x - b_j|_2 for nrhs right-hand sides, Q never stored -----------------------------------------
+ * stmmqr_ls_create, once per pattern and nrhs (1 <= nrhs <= STMMQR_LS_MAX_NRHS, else STMMQR_ERR_INVALID naming the limit): the
+ * columns of A alone are ordered as stmmqr_sparseqr orders them (same `ordering` values, same refusals; Quser with ordering 3 must be
+ * a permutation of 0 .. n-1), the B columns follow unpermuted, stmmqr_analyze runs on the pattern [A | nrhs dense columns] and an R-only
+ * plan is created (device -2: the host half only, no device is touched).  Column singletons are NOT removed in this mode: they come
+ * first in the column order and stay in the matrix (their rows must reach B).  The analysis holds m * nrhs more indices than A's.
+ * stmmqr_ls_solve, any number of times: puts [Ax | B] together on the device (Ax NULL: the values given at create; ax_on_device: Ax is a
+ * device pointer; on_device: B, X and resid are device pointers), factorizes with ntol = n and calls stmmqr_plan_solve_carried.  Nothing
+ * is analysed or planned again.  tol follows stmmqr_sparseqr's rule on the columns of A only (tol <= -2: 20 (m + n) eps max_j |A(:,j)|_2,
+ * recomputed whenever values are given -- device values are copied back once for it; -2 < tol < 0: no rank detection).
+ * B m x nrhs (ldb >= m), X n x nrhs (ldx >= n), resid [nrhs] or NULL.
+ * info[0..13] = rank of A (rank1), nf, flops, flop bound, device ms of the factorization, device ms of the back substitution (transfer of
+ * X included), device bytes (plan + values), retries, reschedules, analyses made, plans made, solves, tol used, nrhs. */
+#define STMMQR_LS_MAX_NRHS 64
+typedef struct stmmqr_ls stmmqr_ls;
+int stmmqr_ls_create(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
+                     stm_long nrhs, const stm_long *Quser, const stmmqr_relax *relax, int device, stmmqr_ls **out);
+int stmmqr_ls_solve(stmmqr_ls *ls, const double *Ax, int ax_on_device, const double *B, stm_long ldb, double *X, stm_long ldx,
+                    double *resid, int on_device);
+const stm_qr_symbolic *stmmqr_ls_symbolic_view(const stmmqr_ls *ls);
+stmmqr_plan *stmmqr_ls_plan(stmmqr_ls *ls);
+int stmmqr_ls_info(const stmmqr_ls *ls, double *info);
+int stmmqr_ls_resid(const stmmqr_ls *ls, double *resid);   /* [nrhs] host array: the residual norms of the last solve */
+void stmmqr_ls_free(stmmqr_ls *ls);
 
 void stmmqr_shutdown(void);                           /* optional end-of-use call for dlopen()ing hosts: device sync  */
 /* Device buffers for hosts without HIP bindings of their own (FFI callers of stmmqr_export_front_dev /

@@ -150,6 +150,7 @@ lib.stmmqr_plan_keep_h.argtypes = [C.c_void_p]
 lib.stmmqr_plan_spmv.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int]
 lib.stmmqr_plan_solve_seminormal.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int,
                                              c_double_p]
+lib.stmmqr_plan_solve_carried.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_set_keep_h.argtypes = [C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_solve_seminormal.argtypes = [C.c_void_p, c_long_p, c_long_p, c_double_p, c_double_p, C.c_long, C.c_long, c_double_p,
                                                  C.c_long, C.c_int, c_double_p]
@@ -334,7 +335,8 @@ class HipQR:
 
     def close(self):
         if getattr(self, "_h", None):
-            lib.stmmqr_plan_destroy(self._h)
+            if not getattr(self, "_borrowed", False):          # (LeastSquares.plan(): the object owns the plan)
+                lib.stmmqr_plan_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -571,6 +573,17 @@ class HipQR:
         _check(lib.stmmqr_plan_solve_seminormal(self._h, Bf.ctypes.data, m, X.ctypes.data, n, Bf.shape[1], int(refine), 0, C.byref(info)),
                "stmmqr_plan_solve_seminormal")
         return (X[:, 0] if np.ndim(B) == 1 else X), float(info.value)
+
+    def solve_carried(self, nrhs: int):
+        """Least squares with the right-hand sides carried through the factorization: the plan holds [A B] factorized with
+        ntol = n (n = columns - nrhs, Qfill the identity on the B columns).  Returns (X, resid): X (n x nrhs) = E R11^-1 C with
+        C = Q'B read from the last columns of R, resid[j] = |b_j - A x_j|_2 from the block below C.  Reads R only."""
+        nrhs = int(nrhs)
+        n = self.sym["n"] - nrhs
+        X = np.zeros((max(n, 0), max(nrhs, 0)), order="F")
+        resid = np.zeros(max(nrhs, 1))
+        _check(lib.stmmqr_plan_solve_carried(self._h, nrhs, X.ctypes.data, max(n, 1), resid.ctypes.data, 0), "stmmqr_plan_solve_carried")
+        return X, resid[:nrhs]
 
     def solve(self, B: np.ndarray) -> np.ndarray:
         """QR_solve(QR_RETX_EQUALS_B) (SparseQR.h:411-417): X = E R^-1 (Q'B)(1:n), least-squares solution; rank == n only."""
@@ -964,6 +977,98 @@ class SparseQR:
         X = np.zeros((rows, B.shape[1]), order="F")
         _check(lib.stmmqr_sparseqr_solve(self._h, system, _dp(B), B.shape[0], B.shape[1], _dp(X), rows), "stmmqr_sparseqr_solve")
         return X
+
+
+lib.stmmqr_ls_create.argtypes = [C.c_int, C.c_double, C.c_long, C.c_long, c_long_p, c_long_p, c_double_p, C.c_long, c_long_p, C.POINTER(Relax),
+                                 C.c_int, C.POINTER(C.c_void_p)]
+lib.stmmqr_ls_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
+lib.stmmqr_ls_symbolic_view.restype = C.POINTER(QrSymbolicC)
+lib.stmmqr_ls_symbolic_view.argtypes = [C.c_void_p]
+lib.stmmqr_ls_plan.restype = C.c_void_p
+lib.stmmqr_ls_plan.argtypes = [C.c_void_p]
+lib.stmmqr_ls_info.argtypes = [C.c_void_p, c_double_p]
+lib.stmmqr_ls_resid.argtypes = [C.c_void_p, c_double_p]
+lib.stmmqr_ls_free.restype = None
+lib.stmmqr_ls_free.argtypes = [C.c_void_p]
+
+
+class LeastSquares:
+    """min |A x - b| for nrhs right-hand sides with the right-hand sides carried through the factorization (stmmqr_ls_*): the
+    columns of A are ordered as SparseQR orders them, [A B] is analysed once and factorized with ntol = n at every solve, and
+    x = E R11^-1 C comes from R alone -- Q is never stored (an R-only plan).  Column singletons are not removed in this mode.
+    solve() may be called again with new values and a new B (a Gauss-Newton loop): nothing is analysed or planned again.
+    symbolic_only=True stops after the host half (no GPU needed)."""
+
+    def __init__(self, m, n, Ap, Ai, Ax, nrhs=1, ordering=7, tol=-2.0, relax: Relax | None = None, Quser=None, device=-1,
+                 symbolic_only=False):
+        self.m, self.n, self.nrhs = int(m), int(n), int(nrhs)
+        Ap = np.ascontiguousarray(Ap, I64); Ai = np.ascontiguousarray(Ai, I64); Ax = np.ascontiguousarray(Ax, np.float64)
+        Q = None if Quser is None else np.ascontiguousarray(Quser, I64)
+        if Q is not None and Q.size != self.n:
+            raise StmmqrError("LeastSquares: Quser must hold one entry per column of A")
+        self.anz = int(Ap[-1])
+        self._h = C.c_void_p()
+        _check(lib.stmmqr_ls_create(int(ordering), float(tol), self.m, self.n, _ip(Ap), _ip(Ai), _dp(Ax), self.nrhs, _ip(Q),
+                                    None if relax is None else C.byref(relax), -2 if symbolic_only else int(device), C.byref(self._h)),
+               "stmmqr_ls_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.stmmqr_ls_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def symbolic(self) -> dict:
+        """the qr_symbolic of [A B] (n = columns of A + nrhs; Qfill = A's order, then the identity)"""
+        S = lib.stmmqr_ls_symbolic_view(self._h).contents
+        return _symbolic_dict(S, S.m, S.n)
+
+    def plan(self) -> HipQR:
+        """the R-only device plan of [A B] as a HipQR (borrowed: valid until close(); download / rsolve / solve_carried / device_bytes)"""
+        h = lib.stmmqr_ls_plan(self._h)
+        if not h:
+            raise StmmqrError("LeastSquares.plan: the object holds the host half only")
+        S = lib.stmmqr_ls_symbolic_view(self._h).contents
+        p = HipQR.__new__(HipQR)
+        p._keep, p._borrowed, p._h = {}, True, h
+        p.sym = {k: int(getattr(S, k)) for k in ["m", "n", "anz", "nf", "maxfn", "rjsize", "hisize"]}
+        return p
+
+    @property
+    def info(self) -> dict:
+        v = np.zeros(14)
+        _check(lib.stmmqr_ls_info(self._h, _dp(v)), "stmmqr_ls_info")
+        keys = ["rank", "nf", "flops", "flop_bound", "ms_factorize", "ms_solve", "device_bytes", "retries", "reschedules", "analyses",
+                "plans", "solves", "tol", "nrhs"]
+        return dict(zip(keys, v.tolist()))
+
+    def solve(self, B, Ax=None):
+        """-> (X, resid): X n x nrhs (a vector for a vector B), resid[j] = |b_j - A x_j|_2.  Ax: new values of A (same pattern)."""
+        Bf = np.array(B, dtype=np.float64, order="F", copy=True).reshape(self.m, -1, order="F")
+        if Bf.shape[1] != self.nrhs:
+            raise StmmqrError(f"LeastSquares.solve: B has {Bf.shape[1]} columns, the object was created for {self.nrhs}")
+        if Ax is not None:
+            Ax = np.ascontiguousarray(Ax, np.float64)
+            if Ax.size != self.anz:
+                raise StmmqrError("LeastSquares.solve: Ax must hold one value per entry of A's pattern")
+        X = np.zeros((self.n, self.nrhs), order="F")
+        resid = np.zeros(self.nrhs)
+        _check(lib.stmmqr_ls_solve(self._h, None if Ax is None else Ax.ctypes.data, 0, Bf.ctypes.data, max(self.m, 1), X.ctypes.data,
+                                   max(self.n, 1), resid.ctypes.data, 0), "stmmqr_ls_solve")
+        return (X[:, 0] if np.ndim(B) == 1 else X), resid
+
+    def solve_dev(self, b_ptr: int, x_ptr: int, ax_ptr: int | None = None, resid=True):
+        """device pointers: B (m x nrhs, ld m), X (n x nrhs, ld n), optionally A's values.  resid: True -> the residual norms as a
+        numpy array, an int -> a device pointer that receives them (returns None), False / None -> not asked for."""
+        rd = None if resid is True or resid in (False, None) else C.c_void_p(int(resid))
+        _check(lib.stmmqr_ls_solve(self._h, None if ax_ptr is None else C.c_void_p(int(ax_ptr)), 1, C.c_void_p(int(b_ptr)), max(self.m, 1),
+                                   C.c_void_p(int(x_ptr)), max(self.n, 1), rd, 1), "stmmqr_ls_solve")
+        if resid is True:
+            out = np.zeros(self.nrhs)
+            _check(lib.stmmqr_ls_resid(self._h, _dp(out)), "stmmqr_ls_resid")
+            return out
+        return None
 
 
 def read_matrix_market(path):

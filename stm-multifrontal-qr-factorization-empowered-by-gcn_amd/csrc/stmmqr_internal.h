@@ -18,6 +18,10 @@ void stm_aop_destroy(stm_aop *op);
 // host arrays: Y = A X (trans 0), A' X (trans 1), or with B (trans 0) Y = B - A X
 int stm_aop_apply(stm_aop *op, int trans, const double *X, stm_long ldx, const double *B, stm_long ldb, double *Y, stm_long ldy,
                   stm_long nrhs);
+// QR_DEFAULT_TOL of a matrix, and the column order stmmqr_sparseqr gives it (Q: [n]; orderings and refusals as stmmqr_sparseqr)
+double stm_qr_default_tol(stm_long m, stm_long n, const stm_long *Ap, const double *Ax);
+int stm_sparseqr_order(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
+                       const stm_long *Quser, stm_long *Q);
 // m, n of a factorized SparseQR object (stmmqr_sparseqr.cpp)
 int stm_sparseqr_dims(const stmmqr_qr *qr, stm_long *m, stm_long *n);
 }

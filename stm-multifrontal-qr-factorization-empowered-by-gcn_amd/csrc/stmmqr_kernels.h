@@ -117,6 +117,10 @@ int stm_launch_spmv(int rows, const int *ptr, const int *idx, const int *vpos, c
                     const double *B, long long ldb, double *Y, long long ldy, long long nrhs, hipStream_t st);
 int stm_launch_colnorm2(long long rows, const double *X, long long ldx, int ncols, double *out, hipStream_t st);
 int stm_launch_add_cols(int rows, int ncols, const double *D, long long ldd, double *X, long long ldx, hipStream_t st);
+// right-hand sides carried through the factorization (stmmqr_carried.hip): the view of the fronts that hold B columns as pivots
+// (live A pivots -> view[f].rank, residual norms of the B columns), and x(n + j0 + r) = -1 in vector r of a batch
+int stm_launch_carried_view(const DevCtx &c, const int *flist, int nfr, int n, FrontNum *view, double *resid, hipStream_t st);
+int stm_launch_carried_seed(double *X, long long ldx, int n, int j0, int nb, hipStream_t st);
 // Q-apply / triangular solve on the resident factors
 // Several right-hand sides per launch (QR_qmult / QR_solve take blocks of them: qr_panel, SparseQR.c:1591-1706): every kernel of
 // these operations takes right-hand side blockIdx.y (or .z) of a BATCH -- the same workgroups, one set per vector, in the same

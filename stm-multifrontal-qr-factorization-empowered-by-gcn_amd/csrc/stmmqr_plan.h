@@ -216,6 +216,12 @@ struct stmmqr_plan {
     std::vector<int> h_smap;                    // host copy of d_smap (what those forms are built from)
     bool a_index_ready = false;
     DevBuf<double> d_csB, d_csX, d_csR, d_csZ, d_csY, d_csD, d_csN;   // the seminormal solve's vectors (grown on demand)
+    // stmmqr_plan_solve_carried: the view of the factorization that ends at column n (FrontSym with fp cut back to the A pivots,
+    // FrontNum with the live A pivots as rank), the fronts that hold B pivots, the residual norms
+    DevBuf<FrontSym> d_fs_car;
+    DevBuf<FrontNum> d_fnum_car;
+    DevBuf<int> d_carlist;
+    DevBuf<double> d_carN;
 
     // results of the last factorization
     bool factored = false, begun = false, first_group = true;
@@ -274,6 +280,7 @@ struct stmmqr_plan {
         add(d_wcnt); add(d_wcnt2); add(d_wflag); add(d_wflag2); add(d_Rboff); add(d_Rdead); add(d_Ypend); add(d_ypoff);
         add(d_rhtop); add(d_fin); add(d_kept); add(d_scr); add(d_bounce); add(d_fs_scr);
         add(d_Acp); add(d_Aci); add(d_Arp); add(d_Arj); add(d_Arq);
+        add(d_fs_car); add(d_fnum_car); add(d_carlist); add(d_carN);
         return b;
     }
     DevCtx ctx() const

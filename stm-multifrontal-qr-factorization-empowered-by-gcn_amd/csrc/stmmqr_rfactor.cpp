@@ -652,6 +652,92 @@ int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ld
     return check_device_err(P, "internal: live pivot count of a front differs from its rank");
 }
 
+// Least squares with the right-hand sides carried through the factorization; see include/stmmqr_hip.h.  The plan holds the R of
+// [A B] (n = P.n - nrhs columns of A, ntol = n).  The back substitution is rsolve_vector's pass over the tree on a view of the
+// factorization that ends at column n (stmmqr_carried.hip): fronts that hold B columns as pivots have fp cut back to their A pivots
+// and their live A pivots as rank, y = 0 and x(n + j) = -1 for right-hand side j -- so y - R12 x is C(:, j) minus the A part, and
+// no diagonal entry of the B block is ever a divisor.
+int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_long ldx, double *resid, int on_device)
+{
+    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    stmmqr_plan &P = *plan;
+    if (nrhs < 1 || nrhs > P.n) return fail(STMMQR_ERR_INVALID, "carried solve: nrhs must be between 1 and the number of columns of the factorized [A B]");
+    const long m = P.m, na = P.n, n = P.n - nrhs;
+    if (!X || ldx < n) return fail(STMMQR_ERR_INVALID, "bad carried solve arguments");
+    if (P.last_ntol != n)
+        return fail(STMMQR_ERR_INVALID, "carried solve: the factorization was made with ntol = " + std::to_string(P.last_ntol) + ", not n = " +
+                                            std::to_string(n) + " (the columns of B must not be rank-tested, those of A must)");
+    if (P.has_qfill)
+        for (long j = n; j < na; j++)
+            if (P.Qfill[(size_t)j] != j)
+                return fail(STMMQR_ERR_INVALID, "carried solve: column " + std::to_string(j) + " of [A B] is permuted (Qfill must be the identity on the B columns)");
+    HIPCHK(hipSetDevice(P.device));
+    LCHK(ensure_rowmap(P));
+    hipStream_t st = P.stream;
+    const auto &LV = P.glevels[0];
+    // ---- the view: FrontSym of the array the resident-factor kernels read (res_ctx) with fp cut back, the B fronts level by level ----
+    std::vector<FrontSym> vs = P.recycle ? P.fs_scr : P.fs;
+    if (P.recycle)
+        for (long f = 0; f < P.nf; f++)
+            if (P.kept[(size_t)f]) vs[(size_t)f].foff = (long long)((P.d_F.p + P.fs[f].foff) - P.d_scr.p);     // (as ensure_scratch)
+    std::vector<int> blist, boff(LV.size() + 1, 0);
+    for (size_t l = 0; l < LV.size(); l++) {
+        for (int q = 0; q < LV[l].n_all; q++) {
+            const int f = P.lists[LV[l].all_off + q];
+            const FrontSym &s = P.fs[f];
+            if ((long)s.col1 + s.fp > n) { blist.push_back(f); vs[(size_t)f].fp = (int)std::max(0L, n - (long)s.col1); }
+        }
+        boff[l + 1] = (int)blist.size();
+    }
+    if (blist.empty()) blist.push_back(0);
+    if (P.d_fs_car.n != vs.size()) LCHK(P.d_fs_car.alloc(vs.size()));
+    if (P.d_carlist.n < blist.size()) LCHK(P.d_carlist.alloc(blist.size()));
+    if (!vs.empty()) HIPCHK(hipMemcpyAsync(P.d_fs_car.p, vs.data(), vs.size() * sizeof(FrontSym), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(P.d_carlist.p, blist.data(), blist.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                            // (vs / blist are pageable and local)
+    if (P.d_fnum_car.n != (size_t)std::max(1L, P.nf)) LCHK(P.d_fnum_car.alloc((size_t)std::max(1L, P.nf)));
+    if (P.nf > 0) HIPCHK(hipMemcpyAsync(P.d_fnum_car.p, P.d_fnum.p, (size_t)P.nf * sizeof(FrontNum), hipMemcpyDeviceToDevice, st));
+    LCHK(grow(P.d_carN, (size_t)nrhs));
+    HIPCHK(hipMemsetAsync(P.d_carN.p, 0, (size_t)nrhs * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
+    if ((size_t)(std::max(1L, n) * nrhs) > P.d_Yall.n) LCHK(P.d_Yall.alloc((size_t)(std::max(1L, n) * nrhs)));
+    const DevCtx ct = res_ctx(P);
+    DevCtx cv = ct;
+    cv.fs = P.d_fs_car.p; cv.fnum = P.d_fnum_car.p;
+    const int *L0 = P.d_lists.p;
+    const int nbmax = rhs_batch_max();
+    for (stm_long j0 = 0; j0 < nrhs; j0 += nbmax) {
+        const int nb = (int)std::min<stm_long>(nbmax, nrhs - j0);
+        LCHK(ensure_rhs_batch(P, nb));
+        const RhsBatch B = rhs_strides(P);
+        HIPCHK(hipMemsetAsync(P.d_W.p, 0, (size_t)nb * (size_t)std::max(1L, m) * sizeof(double), st));
+        HIPCHK(hipMemsetAsync(P.d_Xs.p, 0, (size_t)nb * (size_t)na * sizeof(double), st));
+        LCHK(stm_launch_carried_seed(P.d_Xs.p, B.x, (int)n, (int)j0, nb, st));
+        for (size_t l = LV.size(); l-- > 0;) {
+            LCHK(level_to_front_form(P, l));
+            // (the first pass sets the view's ranks of the level's B fronts before its kernels read them, and takes the residual norms
+            //  while the level is in front form)
+            if (j0 == 0) LCHK(stm_launch_carried_view(ct, P.d_carlist.p + boff[l], boff[l + 1] - boff[l], (int)n, P.d_fnum_car.p, P.d_carN.p, st));
+            LCHK(stm_launch_rsolve(cv, L0 + LV[l].all_off, LV[l].n_all, P.d_Rj.p, P.d_W.p, P.d_Xs.p, P.level_lds_rs[l], P.d_err.p, st, nb, B));
+            const auto &Q = P.level_qbig[l];
+            LCHK(stm_launch_rsolve_big(cv, P.d_qb.p + Q.off, Q.n, Q.live_rsteps, Q.max_nslab, P.d_Rj.p, P.d_W.p, P.d_Xs.p, P.d_Xf.p,
+                                       P.d_Dq.p, P.d_Rm.p + Q.off, P.d_err.p, st, nb, B));
+        }
+        LCHK(stm_launch_perm(P.d_Xs.p, P.has_qfill ? P.d_Qfill.p : nullptr, P.d_Yall.p + j0 * n, (int)n, 1, st, nb, na, n));   // X[Qfill[j]] = x[j], j < n
+    }
+    if (on_device) {
+        if (n > 0)
+            HIPCHK(hipMemcpy2DAsync(X, (size_t)ldx * sizeof(double), P.d_Yall.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
+                                    (size_t)nrhs, hipMemcpyDeviceToDevice, st));
+        if (resid) HIPCHK(hipMemcpyAsync(resid, P.d_carN.p, (size_t)nrhs * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+    } else {
+        if (resid) HIPCHK(hipMemcpyAsync(resid, P.d_carN.p, (size_t)nrhs * sizeof(double), hipMemcpyDeviceToHost, st));
+        LCHK(download_cols(P, P.d_Yall, X, ldx, n, nrhs));
+    }
+    return check_device_err(P, "internal: live pivot count of a front differs from its rank");
+}
+
 int stmmqr_plan_keep_h(const stmmqr_plan *plan) { return plan ? plan->keep_h : -1; }
 
 // ---- a caller's matrix on the device (the sparseqr-level seminormal solve: products with the FULL A, singletons included) ----

@@ -107,6 +107,24 @@ struct stmmqr_qr {
 
 extern "C" {
 
+// QR_DEFAULT_TOL: 20 (m + n) eps max_j |A(:,j)|_2  (qr_tol / qr_maxcolnorm, SparseQR.c:126-130,1134-1144,1376-1420)
+double stm_qr_default_tol(stm_long m, stm_long n, const stm_long *Ap, const double *Ax)
+{
+    double mx = 0;
+    for (Long j = 0; j < n; j++) {
+        // (dnrm2's scaled form: the largest entry carries the magnitude)
+        double scale = 0, ssq = 1;
+        for (Long p = Ap[j]; p < Ap[j + 1]; p++) {
+            const double a = std::fabs(Ax[p]);
+            if (a == 0) continue;
+            if (scale < a) { ssq = 1 + ssq * (scale / a) * (scale / a); scale = a; }
+            else ssq += (a / scale) * (a / scale);
+        }
+        mx = std::max(mx, scale * std::sqrt(ssq));
+    }
+    return std::min(20.0 * ((double)m + (double)n) * DBL_EPSILON * mx, DBL_MAX);
+}
+
 static int numeric_impl(stmmqr_qr *QR, int device);
 
 static int sparseqr_impl(int ordering, double tol, Long m, Long n, const Long *Ap, const Long *Ai, const double *Ax, const Long *Quser,
@@ -125,23 +143,7 @@ static int sparseqr_impl(int ordering, double tol, Long m, Long n, const Long *A
     const bool fill_reducing = (ordering == COLAMD);
     std::unique_ptr<stmmqr_qr> QR(new stmmqr_qr());
     QR->m = m; QR->n = n;
-    if (tol <= -2) {
-        // QR_DEFAULT_TOL: 20 (m + n) eps max_j |A(:,j)|_2  (qr_tol / qr_maxcolnorm, SparseQR.c:126-130,1134-1144,1376-1420)
-        double mx = 0;
-        for (Long j = 0; j < n; j++) {
-            // (dnrm2's scaled form: the largest entry carries the magnitude)
-            double scale = 0, ssq = 1;
-            for (Long p = Ap[j]; p < Ap[j + 1]; p++) {
-                const double a = std::fabs(Ax[p]);
-                if (a == 0) continue;
-                if (scale < a) { ssq = 1 + ssq * (scale / a) * (scale / a); scale = a; }
-                else ssq += (a / scale) * (a / scale);
-            }
-            mx = std::max(mx, scale * std::sqrt(ssq));
-        }
-        tol = 20.0 * ((double)m + (double)n) * DBL_EPSILON * mx;
-        tol = std::min(tol, DBL_MAX);
-    }
+    if (tol <= -2) tol = stm_qr_default_tol(m, n, Ap, Ax);
     if (tol < 0) tol = -1;                                                                        // QR_NO_TOL (SparseQR.c:131-135)
     QR->tol = tol;
     const double t_start = wall();
@@ -247,6 +249,7 @@ static int sparseqr_impl(int ordering, double tol, Long m, Long n, const Long *A
     }
     QR->n1cols = n1cols; QR->n1rows = n1rows;
     QR->ordering_used = ordering;
+    if (numeric < 0) { *out = QR.release(); return 0; }                                           // (stm_sparseqr_order: the column order alone)
 
     // ---- R1 (singleton rows, row form) and Y (what is left; SparseQR.c:216-329) ----
     const Long n2 = n - n1cols, m2 = m - n1rows;
@@ -368,6 +371,25 @@ int stmmqr_sparseqr_symbolic(int ordering, double tol, stm_long m, stm_long n, c
     } catch (...) {
         return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_symbolic: internal error");
     }
+}
+
+// the column order stmmqr_sparseqr would use for A (singleton columns first, then the fill-reducing order of the rest), nothing else:
+// no R1 / Y split, no analysis (stmmqr_ls.cpp orders A this way and keeps the singletons in the matrix)
+int stm_sparseqr_order(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
+                       const stm_long *Quser, stm_long *Q)
+{
+    stmmqr_qr *qr = nullptr;
+    try {
+        const int e = sparseqr_impl(ordering, tol, m, n, Ap, Ai, Ax, Quser, nullptr, -1, -1, &qr);
+        if (e) return e;
+    } catch (const std::bad_alloc &) {
+        return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_sparseqr: out of memory");
+    } catch (...) {
+        return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr: internal error");
+    }
+    for (stm_long k = 0; k < n; k++) Q[k] = qr->Q1fill[(size_t)k];
+    delete qr;
+    return 0;
 }
 
 int stmmqr_sparseqr_set_keep_h(stmmqr_qr *qr, int keep)
