@@ -28,9 +28,13 @@ int stmmqr_plan_export_front(stmmqr_plan *plan, stm_long f, double *C, stm_long 
     if (e) return e;
     stmmqr_plan &P = *plan;
     if ((e = stm_check_c_slot(P, f, info[3], "stmmqr_plan_export_front"))) return e;
-    if (info[3] > 0 && C)
+    if (info[3] > 0 && C) {
         HIPCHK(hipMemcpy(C, P.d_C.p + P.fs[f].coff, (size_t)info[3] * sizeof(double),
                          c_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+        // (a device-to-device hipMemcpy may return before the copy has run, and the plans' streams are non-blocking: they are not
+        //  ordered behind the null stream.  The block is complete when this call returns, whatever stream reads it next.)
+        if (c_on_device) HIPCHK(hipStreamSynchronize(nullptr));
+    }
     if (info[2] > 0 && rows) {
         std::vector<int> r32((size_t)info[2]);
         HIPCHK(hipMemcpy(r32.data(), P.d_Hii.p + P.fs[f].hip + info[1], (size_t)info[2] * sizeof(int), hipMemcpyDeviceToHost));
@@ -58,9 +62,13 @@ int stmmqr_plan_import_front(stmmqr_plan *plan, stm_long f, stm_long fm, stm_lon
     memset(&nm, 0, sizeof nm);
     nm.fm = (int)fm; nm.rank = (int)rank; nm.cm = (int)cm; nm.done = 1; nm.g = (int)rank;
     HIPCHK(hipMemcpy(P.d_fnum.p + f, &nm, sizeof nm, hipMemcpyHostToDevice));
-    if (csize > 0)
+    if (csize > 0) {
         HIPCHK(hipMemcpy(P.d_C.p + P.fs[f].coff, C, (size_t)csize * sizeof(double),
                          c_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        // (device to device: the copy is enqueued on the null stream and the call may return before it has run; the parent's
+        //  assembly reads the block on the plan's non-blocking stream, which does not wait for the null stream -- wait here)
+        if (c_on_device) HIPCHK(hipStreamSynchronize(nullptr));
+    }
     if (cm > 0) {
         std::vector<int> r32((size_t)cm);
         for (long i = 0; i < cm; i++) r32[i] = (int)rows[i];
