@@ -150,6 +150,14 @@ static inline __host__ __device__ int stm_quad_slots(int nslf, int tune)
 #define STM_PAIR_MIN_ROWS 16384  // fronts with at least this many (estimated) rows take the pair update (stmmqr_options::pair_update);
                                  // measured: 27 000 rows -12 %, 7818 rows +17 % (and no look-ahead for pair steps)
 
+// Dynamic LDS (bytes) that ONE right-hand side of a front needs in the one-workgroup kernels on the resident factors: k_qapply_t holds
+// the front's rows of x and the reflector numbering, k_rsolve the pivotal and non-pivotal parts of x and the live-column list.  A
+// front that needs more than STM_RES_LDS_MAX takes the split kernels (FrontSym::qbig, planner); the launchers choose the vectors per
+// workgroup from the maximum over a tree level (ensure_rowmap).  The shapes on both sides of every threshold: tests/test_gpu_resident_shapes.py.
+#define STM_RES_LDS_MAX 131072   // hipFuncAttributeMaxDynamicSharedMemorySize of these kernels (stm_configure_resident)
+static inline long stm_lds_qapply(long fm_ub, long fn) { return ((fm_ub + 1) & ~1L) * 8 + fn * 4 + 16; }
+static inline long stm_lds_rsolve(long fp, long fn) { return (((fp + 1) & ~1L) + (fn - fp) + 2) * 8 + fp * 4 + 16; }
+
 #define STM_QB_ROWS 512      // rows of a front per workgroup of the split Q-apply (k_qbig_step)
 // split Q-apply (k_qbig_*): one entry per large front of a tree level
 struct QbDesc {

@@ -795,7 +795,10 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
             // (k_qbig_step4) smaller fronts pay too, at 256 KB of T4 per four panels -- default workload, threshold: Q'b / solve ms,
             // GB of T4: 2 M 13.1 / 20.6, 0.31; 1 M 12.5 / 20.0, 0.39; 256 K 11.9 / 19.5, 0.61; 128 K 11.6 / 19.2, 0.81.  1 M.
             const long qbig_min = getenv("STMMQR_QBIG_MIN") ? atol(getenv("STMMQR_QBIG_MIN")) : (1L << 20);
-            s.qbig = (fm * fn >= qbig_min && fn >= 1) ? 1 : 0;
+            // ... and, whatever its entry count, a front that one workgroup cannot hold in LDS: a tall thin one (16 363 rows at 40
+            // columns) or a short wide one whose columns are all pivotal (10 921 of them) -- the split kernels have no such limit
+            const bool over_lds = stm_lds_qapply(fm, fn) > STM_RES_LDS_MAX || stm_lds_rsolve(fp, fn) > STM_RES_LDS_MAX;
+            s.qbig = ((fm * fn >= qbig_min || over_lds) && fn >= 1) ? 1 : 0;
         }
         s.parent = (int)parent[f];
         s.foff = 0; s.coff = 0;                                    // (assign_arenas, once the groups are known)

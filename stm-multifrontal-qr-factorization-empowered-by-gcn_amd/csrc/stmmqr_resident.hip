@@ -1117,6 +1117,7 @@ int stm_launch_qapply_t(const DevCtx &c, const int *flist, int nfr, int method, 
 {
     if (nfr <= 0) return 0;
     // (lds_bytes: what ONE right-hand side needs; R of them share a workgroup while R x that stays within 64 KB)
+    // (the shapes on both sides of each threshold below: tests/test_gpu_resident_shapes.py)
     if (nb >= 3 && 4L * lds_bytes <= 65536)
         hipLaunchKernelGGL(k_qapply_t<4>, dim3(nfr, (nb + 3) / 4), dim3(QA_NT), (size_t)4 * lds_bytes, st, c, flist, method, W, B, nb);
     else if (nb >= 2 && 2L * lds_bytes <= 131072)
@@ -1166,7 +1167,7 @@ int stm_launch_rsolve(const DevCtx &c, const int *flist, int nfr, const int *Rj,
                       int *err, hipStream_t st, int nb, const RhsBatch &B)
 {
     if (nfr <= 0) return 0;
-    // (lds_bytes: what ONE right-hand side needs)
+    // (lds_bytes: what ONE right-hand side needs; the shapes on both sides of each threshold below: tests/test_gpu_resident_shapes.py)
     if (nb >= 3 && 4L * lds_bytes <= 65536)
         hipLaunchKernelGGL(k_rsolve<4>, dim3(nfr, (nb + 3) / 4), dim3(RS_NT), (size_t)4 * lds_bytes, st, c, flist, Rj, W, X, err, B, nb);
     else if (nb >= 2 && 2L * lds_bytes <= 131072)

@@ -1,5 +1,6 @@
 // stmmqr_rfactor.cpp -- SURVEY.md 8 (f1): QR_qmult / QR_solve on the factors resident in HBM (host side; kernels: stmmqr_resident.hip).
 #include "stmmqr_plan.h"
+#include <climits>
 
 extern "C" {
 
@@ -83,7 +84,7 @@ int ensure_rowmap(stmmqr_plan &P)
             for (int q = 0; q < LV[l].n_all; q++) {
                 const int f = P.lists[LV[l].all_off + q];
                 const FrontSym &s = P.fs[f];
-                const int need = (int)(((s.fm_ub + 1) & ~1) * 8 + s.fn * 4 + 16);
+                const int need = (int)std::min(stm_lds_qapply(s.fm_ub, s.fn), (long)INT_MAX);
                 P.level_lds_rt[l] = std::max(P.level_lds_rt[l], (int)((((s.fn + 1) & ~1) + ((std::min(s.fp, std::max(s.fm_ub, 1)) + 2) & ~1)) * 8 + s.fp * 4 + 32));
                 P.level_lds_qa_all[l] = std::max(P.level_lds_qa_all[l], need);
                 if (s.qbig) {
@@ -110,7 +111,7 @@ int ensure_rowmap(stmmqr_plan &P)
                     Q.max_rsteps = std::max(Q.max_rsteps, (std::min(s.fp, s.fm_ub) + 31) / 32);
                 } else {
                     P.level_lds_qa[l] = std::max(P.level_lds_qa[l], need);
-                    P.level_lds_rs[l] = std::max(P.level_lds_rs[l], (int)((((s.fp + 1) & ~1) + (s.fn - s.fp) + 2) * 8 + s.fp * 4 + 16));
+                    P.level_lds_rs[l] = std::max(P.level_lds_rs[l], (int)std::min(stm_lds_rsolve(s.fp, s.fn), (long)INT_MAX));
                 }
             }
             P.level_qbig[l].t4i_n = (int)P.t4items.size() - P.level_qbig[l].t4i_off;
@@ -155,8 +156,11 @@ int ensure_rowmap(stmmqr_plan &P)
         }
         if (changed && !P.h_qb.empty()) HIPCHK(hipMemcpy(P.d_qb.p, P.h_qb.data(), P.h_qb.size() * sizeof(QbDesc), hipMemcpyHostToDevice));
     }
+    // (the planner sends such fronts to the split kernels, so neither can happen; no launch may ask for more LDS than configured)
     for (int b : P.level_lds_qa)
-        if (b > 131072) return fail(STMMQR_ERR_TOO_LARGE, "a front has more rows than the Q-apply kernel holds in LDS");
+        if (b > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front has more rows than the Q-apply kernel holds in LDS");
+    for (int b : P.level_lds_rs)
+        if (b > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front has more columns than the back-substitution kernel holds in LDS");
     P.rowmap_ready = true;
     return 0;
 }
