@@ -405,6 +405,29 @@ int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ld
  * qr_factorize(..., ntol = n) can use it on the seam's cached plan. */
 int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_long ldx, double *resid, int on_device);
 
+/* Variances of a least-squares fit.  var[j], j < ncol (the caller's column order) = diag(((A E)_live' (A E)_live)^-1), the unscaled
+ * variances of the basic least-squares solution; (A E)_live holds the columns with Rdead == 0.  Dead columns get 0, as the solves give
+ * x = 0 there.  The variance of x_j is var[j] * |b - A x|^2 / (m - rank).
+ * The selected inverse of R'R (Takahashi / Erisman-Tinney) is built front by front from the root to the leaves with dense triangular
+ * solves and matrix products on the fronts held in HBM.  Reads R only: plans with and without H.  No limit on the width of a front.
+ *   ncol = the number of columns of the plan: all of them.
+ *   ncol < that: the plan holds [A B] as stmmqr_plan_solve_carried expects it (ntol = ncol, Qfill the identity on the trailing
+ *   columns: the same messages), and the trailing columns take no part.
+ *   on_device: var is a device pointer.
+ * Device memory of the call alone, released before it returns (stmmqr_plan_device_bytes does not change): the blocks of the
+ * selected inverse, sum over the fronts of (min(fp, fm_ub) + fn - fp)^2 doubles, the widest tree level's R11^-1 [I | R12] and two
+ * index tables of the size of Rj.  No room for them: STMMQR_ERR_OUT_OF_MEMORY, the plan stays usable.
+ * STMMQR_ERR_INVALID (the message says why; the plan stays usable): null plan or nothing factorized, var NULL, ncol out of range, the
+ * carried conditions not met for ncol < n, or a plan that does not hold the whole tree (stmmqr_plan_set_groups, imported or shared
+ * fronts).
+ * Accuracy: the recurrence forms entries of (R'R)^-1, whose condition is cond(A)^2, so an entry carries an error of about
+ * u cond(A)^2 times the largest one -- as the normal equations would.  Up to cond(A) ~ 1e7 every variance has digits to spare
+ * (measured: DESIGN.md 6h); on lns_3937 (cond ~ 1e11) 45 of 1822 variances are off by more than 1e-3 relative and four are negative.
+ * There |stmmqr_plan_rsolve(system 3, e_j)|^2 gives column j to u cond(A), one column at a time.
+ * Out of scope: off-diagonal entries of the inverse as an output, and a stmmqr_sparseqr_* entry (the singleton block R1 lives on the
+ * host and is no part of the plan; the stmmqr_ls object removes no singletons and is the home of this feature). */
+int stmmqr_plan_covariance_diag(stmmqr_plan *plan, stm_long ncol, double *var, int on_device);
+
 /* dense single-front kernels on host buffers (inner seams without the cc argument) */
 stm_long stmmqr_front(stm_long m, stm_long n, stm_long npiv, double tol, stm_long ntol, double *F,
                       stm_long *Stair, char *Rdead, double *Tau, double *flops);
@@ -597,6 +620,7 @@ const stm_qr_symbolic *stmmqr_ls_symbolic_view(const stmmqr_ls *ls);
 stmmqr_plan *stmmqr_ls_plan(stmmqr_ls *ls);
 int stmmqr_ls_info(const stmmqr_ls *ls, double *info);
 int stmmqr_ls_resid(const stmmqr_ls *ls, double *resid);   /* [nrhs] host array: the residual norms of the last solve */
+int stmmqr_ls_covariance_diag(stmmqr_ls *ls, double *var, int on_device);   /* after a solve: stmmqr_plan_covariance_diag with ncol = n of A */
 void stmmqr_ls_free(stmmqr_ls *ls);
 
 void stmmqr_shutdown(void);                           /* optional end-of-use call for dlopen()ing hosts: device sync  */

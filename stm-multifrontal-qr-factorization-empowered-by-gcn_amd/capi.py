@@ -151,6 +151,7 @@ lib.stmmqr_plan_spmv.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_
 lib.stmmqr_plan_solve_seminormal.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int,
                                              c_double_p]
 lib.stmmqr_plan_solve_carried.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
+lib.stmmqr_plan_covariance_diag.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_set_keep_h.argtypes = [C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_solve_seminormal.argtypes = [C.c_void_p, c_long_p, c_long_p, c_double_p, c_double_p, C.c_long, C.c_long, c_double_p,
                                                  C.c_long, C.c_int, c_double_p]
@@ -585,6 +586,19 @@ class HipQR:
         _check(lib.stmmqr_plan_solve_carried(self._h, nrhs, X.ctypes.data, max(n, 1), resid.ctypes.data, 0), "stmmqr_plan_solve_carried")
         return X, resid[:nrhs]
 
+    def covariance_diag(self, ncol=None, dev_ptr=None) -> np.ndarray:
+        """diag(((A E)_live' (A E)_live)^-1) in the caller's column order by selected inversion of R'R on the resident factors: the
+        unscaled variances of the basic least-squares solution, 0 for dead columns.  ncol (default: every column of the plan) smaller
+        than that: the plan holds [A B] as solve_carried expects it and the trailing columns take no part.  dev_ptr: a device
+        pointer that receives the ncol doubles (returns None).  Reads R only; no limit on the width of a front."""
+        ncol = self.sym["n"] if ncol is None else int(ncol)
+        if dev_ptr is not None:
+            _check(lib.stmmqr_plan_covariance_diag(self._h, ncol, C.c_void_p(int(dev_ptr)), 1), "stmmqr_plan_covariance_diag")
+            return None
+        var = np.zeros(max(ncol, 1))
+        _check(lib.stmmqr_plan_covariance_diag(self._h, ncol, var.ctypes.data, 0), "stmmqr_plan_covariance_diag")
+        return var[:max(ncol, 0)]
+
     def solve(self, B: np.ndarray) -> np.ndarray:
         """QR_solve(QR_RETX_EQUALS_B) (SparseQR.h:411-417): X = E R^-1 (Q'B)(1:n), least-squares solution; rank == n only."""
         m, n = self.sym["m"], self.sym["n"]
@@ -988,6 +1002,7 @@ lib.stmmqr_ls_plan.restype = C.c_void_p
 lib.stmmqr_ls_plan.argtypes = [C.c_void_p]
 lib.stmmqr_ls_info.argtypes = [C.c_void_p, c_double_p]
 lib.stmmqr_ls_resid.argtypes = [C.c_void_p, c_double_p]
+lib.stmmqr_ls_covariance_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_ls_free.restype = None
 lib.stmmqr_ls_free.argtypes = [C.c_void_p]
 
@@ -1069,6 +1084,27 @@ class LeastSquares:
             _check(lib.stmmqr_ls_resid(self._h, _dp(out)), "stmmqr_ls_resid")
             return out
         return None
+
+    def variances(self, dev_ptr=None):
+        """after solve(): diag((A_live' A_live)^-1) in A's column order, 0 for dead columns (stmmqr_ls_covariance_diag).  dev_ptr: a
+        device pointer that receives the n doubles (returns None)."""
+        if dev_ptr is not None:
+            _check(lib.stmmqr_ls_covariance_diag(self._h, C.c_void_p(int(dev_ptr)), 1), "stmmqr_ls_covariance_diag")
+            return None
+        var = np.zeros(max(self.n, 1))
+        _check(lib.stmmqr_ls_covariance_diag(self._h, var.ctypes.data, 0), "stmmqr_ls_covariance_diag")
+        return var[:self.n]
+
+    def std_errors(self) -> np.ndarray:
+        """after solve(): the standard errors of x, n x nrhs: sqrt(var * resid_j^2 / (m - rank)) for right-hand side j; inf where
+        m == rank (no degree of freedom left)."""
+        var = self.variances()
+        resid = np.zeros(self.nrhs)
+        _check(lib.stmmqr_ls_resid(self._h, _dp(resid)), "stmmqr_ls_resid")
+        dof = self.m - int(self.info["rank"])
+        if dof <= 0:
+            return np.full((self.n, self.nrhs), np.inf)
+        return np.sqrt(var[:, None] * (resid[None, :] ** 2 / dof))
 
 
 def read_matrix_market(path):

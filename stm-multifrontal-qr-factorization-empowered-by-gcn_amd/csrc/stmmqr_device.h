@@ -168,6 +168,20 @@ struct QbDesc {
                              // front's fm / rank: the panels behind the column where the rows ran out are not visited)
 };
 
+// Selected inversion (stmmqr_selinv.hip, stmmqr_plan_covariance_diag).  The launchers choose no kernel by size: these are the
+// block sizes at which a front gets one more block row, strip or tile (tests/test_gpu_selinv.py sits on both sides of each).
+#define STM_SI_NB 32         // block rows of the back substitution [G | S] = R11^-1 [I | R12] and columns of a workgroup's strip
+#define STM_SI_TILE 64       // output tile of a workgroup of the product kernel (Z_PN, Z_PP)
+#define STM_SI_KC 16         // ... columns of the operands per pass through LDS
+// one front of the VIEW the recurrence walks (all columns of the plan, or the A part of a plan that holds [A B])
+struct SiDesc {
+    long long zoff;          // the front's block of Z in the arena: (rmax + cn)^2 doubles, ld = rmax + cn, live pivots first
+    long long woff;          // its [G | S] in the level's workspace: max(rmax, 1) x (rmax + cn), ld = max(rmax, 1)
+    int fp, cn;              // pivotal columns (cut back to the A pivots) and non-pivotal columns (those with Rj < ncol) of the view
+    int rmax;                // min(fp, fm_ub): bound on the live pivots
+    int check;               // 1: fp is the front's own, so the live count must equal FrontNum::rank
+};
+
 // numeric, written by the kernels
 struct FrontNum {
     int fm;                  // rows of F                           (qr_fsize)

@@ -121,6 +121,11 @@ int stm_launch_add_cols(int rows, int ncols, const double *D, long long ldd, dou
 // (live A pivots -> view[f].rank, residual norms of the B columns), and x(n + j0 + r) = -1 in vector r of a batch
 int stm_launch_carried_view(const DevCtx &c, const int *flist, int nfr, int n, FrontNum *view, double *resid, hipStream_t st);
 int stm_launch_carried_seed(double *X, long long ldx, int n, int j0, int nb, hipStream_t st);
+// selected inversion of R'R (stmmqr_selinv.hip): live-column lists and position tables of every front, then the kernels of one tree
+// level (gather, [G | S], the two products, the diagonal) -- max_r / max_cn: the largest SiDesc::rmax / cn of the level's fronts
+int stm_launch_si_prep(const DevCtx &c, int nf, const SiDesc *sd, int *Lc, int *Pos, int *Rm, int *err, hipStream_t st);
+int stm_launch_si_level(const DevCtx &c, const int *flist, int nfr, int max_r, int max_cn, const SiDesc *sd, const int *Rm, const int *Lc,
+                        const int *Pos, const int *Rj, const int *Qfill, double *W, double *Z, double *var, hipStream_t st);
 // Q-apply / triangular solve on the resident factors
 // Several right-hand sides per launch (QR_qmult / QR_solve take blocks of them: qr_panel, SparseQR.c:1591-1706): every kernel of
 // these operations takes right-hand side blockIdx.y (or .z) of a BATCH -- the same workgroups, one set per vector, in the same

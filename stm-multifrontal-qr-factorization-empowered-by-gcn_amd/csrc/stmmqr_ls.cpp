@@ -199,6 +199,15 @@ int stmmqr_ls_resid(const stmmqr_ls *ls, double *resid)
     return 0;
 }
 
+// the unscaled variances of the last solve's x: diag((A_live' A_live)^-1) from the R of [A B] the object holds (the A part of the view)
+int stmmqr_ls_covariance_diag(stmmqr_ls *ls, double *var, int on_device)
+{
+    if (!ls) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_covariance_diag: null object");
+    if (!ls->plan) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_covariance_diag: the object holds the host half only (device = -2 at create)");
+    if (ls->nsolves < 1) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_covariance_diag: no solve yet");
+    return stmmqr_plan_covariance_diag(ls->plan, ls->n, var, on_device);
+}
+
 void stmmqr_ls_free(stmmqr_ls *ls) { delete ls; }
 
 }  // extern "C"

@@ -742,6 +742,88 @@ int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_l
     return check_device_err(P, "internal: live pivot count of a front differs from its rank");
 }
 
+// diag(((A E)_live' (A E)_live)^-1) by selected inversion of R'R; see include/stmmqr_hip.h and stmmqr_selinv.hip.  The frontal tree is
+// walked from the root to the leaves, a level at a time: every front's block of Z is built from its parent's.  Device memory of the
+// call alone (released before it returns): the arena of the blocks, sum over fronts of (min(fp, fm_ub) + cn)^2 doubles; the widest
+// level's [G | S], sum over its fronts of min(fp, fm_ub) (min(fp, fm_ub) + cn) doubles; two int tables of the size of Rj.
+// ncol < n: the view of stmmqr_plan_solve_carried (fp cut back to the A pivots, their live ones as rank) with fn cut back to the
+// columns of A as well -- the B columns are the last entries of every front's list.
+int stmmqr_plan_covariance_diag(stmmqr_plan *plan, stm_long ncol, double *var, int on_device)
+{
+    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    stmmqr_plan &P = *plan;
+    const long n = P.n;
+    if (!var) return fail(STMMQR_ERR_INVALID, "covariance: var is NULL");
+    if (ncol < 0 || ncol > n)
+        return fail(STMMQR_ERR_INVALID, "covariance: ncol = " + std::to_string(ncol) + " is not between 0 and the " + std::to_string(n) + " columns of the plan");
+    if (ncol < n) {                                          // (the conditions and messages of stmmqr_plan_solve_carried)
+        if (P.last_ntol != ncol)
+            return fail(STMMQR_ERR_INVALID, "carried solve: the factorization was made with ntol = " + std::to_string(P.last_ntol) + ", not n = " +
+                                                std::to_string(ncol) + " (the columns of B must not be rank-tested, those of A must)");
+        if (P.has_qfill)
+            for (long j = ncol; j < n; j++)
+                if (P.Qfill[(size_t)j] != j)
+                    return fail(STMMQR_ERR_INVALID, "carried solve: column " + std::to_string(j) + " of [A B] is permuted (Qfill must be the identity on the B columns)");
+    }
+    bool whole = P.glevels.size() == 1;
+    for (long f = 0; f < P.nf && whole; f++) whole = P.group[(size_t)f] == 0 && !((size_t)f < P.shared.size() && P.shared[(size_t)f]);
+    if (!whole)
+        return fail(STMMQR_ERR_INVALID, "covariance: the plan does not hold the whole tree in one group (groups were set, or fronts are imported or shared)");
+    HIPCHK(hipSetDevice(P.device));
+    LCHK(ensure_rowmap(P));
+    if (ncol == 0) return 0;
+    hipStream_t st = P.stream;
+    const auto &LV = P.glevels[0];
+    const long nf = P.nf;
+    // ---- the view and where every front's block lies ----
+    std::vector<SiDesc> sd((size_t)std::max(1L, nf));
+    std::vector<int> lev_r(LV.size(), 0), lev_cn(LV.size(), 0);
+    long long zall = 0, wmax = 1;
+    for (size_t l = 0; l < LV.size(); l++) {
+        long long w = 0;
+        for (int q = 0; q < LV[l].n_all; q++) {
+            const int f = P.lists[LV[l].all_off + q];
+            const FrontSym &s = P.fs[f];
+            SiDesc &d = sd[(size_t)f];
+            d.fp = (int)std::min<long>(s.fp, std::max(0L, (long)ncol - (long)s.col1));
+            d.check = d.fp == s.fp;
+            d.cn = 0;
+            if (d.check)
+                while (s.fp + d.cn < s.fn && P.Rj[(size_t)(s.rp + s.fp + d.cn)] < ncol) d.cn++;
+            d.rmax = std::min(d.fp, std::max(s.fm_ub, 0));
+            const long long dim = (long long)d.rmax + d.cn;
+            d.zoff = zall; zall += dim * dim;
+            d.woff = w; w += (long long)std::max(d.rmax, 1) * dim;
+            lev_r[l] = std::max(lev_r[l], d.rmax); lev_cn[l] = std::max(lev_cn[l], d.cn);
+        }
+        wmax = std::max(wmax, w);
+    }
+    // ---- the call's own device memory ----
+    DevBuf<double> dZ, dWk, dVar;
+    DevBuf<int> dLc, dPos, dRm;
+    DevBuf<SiDesc> dSd;
+    const size_t rjs = (size_t)std::max(1L, P.rjsize);
+    if (dZ.alloc((size_t)std::max(1LL, zall)) || dWk.alloc((size_t)wmax) || dLc.alloc(rjs) || dPos.alloc(rjs) || dRm.alloc((size_t)std::max(1L, nf)) ||
+        dSd.alloc(sd.size()) || (!on_device && dVar.alloc((size_t)ncol))) {
+        (void)hipGetLastError();
+        return fail(STMMQR_ERR_OUT_OF_MEMORY, "covariance: no device memory for the blocks of the selected inverse (" +
+                                                  std::to_string(8e-9 * ((double)zall + (double)wmax)) + " GB)");
+    }
+    double *dv = on_device ? var : dVar.p;
+    HIPCHK(hipMemcpyAsync(dSd.p, sd.data(), sd.size() * sizeof(SiDesc), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dv, 0, (size_t)ncol * sizeof(double), st));                       // (dead columns: 0)
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
+    const DevCtx c = res_ctx(P);
+    LCHK(stm_launch_si_prep(c, (int)nf, dSd.p, dLc.p, dPos.p, dRm.p, P.d_err.p, st));
+    for (size_t l = LV.size(); l-- > 0;) {
+        LCHK(level_to_front_form(P, l));
+        LCHK(stm_launch_si_level(c, P.d_lists.p + LV[l].all_off, LV[l].n_all, lev_r[l], lev_cn[l], dSd.p, dRm.p, dLc.p, dPos.p, P.d_Rj.p,
+                                 P.has_qfill ? P.d_Qfill.p : nullptr, dWk.p, dZ.p, dv, st));
+    }
+    if (!on_device) HIPCHK(hipMemcpyAsync(var, dv, (size_t)ncol * sizeof(double), hipMemcpyDeviceToHost, st));
+    return check_device_err(P, "internal: live pivot count of a front differs from its rank");      // (synchronizes: sd and the buffers are done with)
+}
+
 int stmmqr_plan_keep_h(const stmmqr_plan *plan) { return plan ? plan->keep_h : -1; }
 
 // ---- a caller's matrix on the device (the sparseqr-level seminormal solve: products with the FULL A, singletons included) ----
