@@ -157,6 +157,13 @@ static inline __host__ __device__ int stm_quad_slots(int nslf, int tune)
 #define STM_RES_LDS_MAX 131072   // hipFuncAttributeMaxDynamicSharedMemorySize of these kernels (stm_configure_resident)
 static inline long stm_lds_qapply(long fm_ub, long fn) { return ((fm_ub + 1) & ~1L) * 8 + fn * 4 + 16; }
 static inline long stm_lds_rsolve(long fp, long fn) { return (((fp + 1) & ~1L) + (fn - fp) + 2) * 8 + fp * 4 + 16; }
+// k_rtsolve's carve: u [fn] (the front's b minus what was solved so far), x [min(fp, max(fm, 1))] (its rows of x; fm <= fm_ub), each
+// rounded up to an even count of doubles, then lc [fp] ints (its live pivot columns)
+static inline long stm_lds_rtsolve(long fp, long fm_ub, long fn)
+{
+    const long fm1 = fm_ub > 1 ? fm_ub : 1;
+    return (((fn + 1) & ~1L) + (((fp < fm1 ? fp : fm1) + 2) & ~1L)) * 8 + fp * 4 + 32;
+}
 
 #define STM_QB_ROWS 512      // rows of a front per workgroup of the split Q-apply (k_qbig_step)
 // split Q-apply (k_qbig_*): one entry per large front of a tree level

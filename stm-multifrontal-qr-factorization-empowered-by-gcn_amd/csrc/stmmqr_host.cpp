@@ -1490,17 +1490,12 @@ int stm_ensure_a_index(stmmqr_plan &P)
             arow[(size_t)p] = rowof[(size_t)r];
             acol[(size_t)p] = (int)(P.has_qfill ? P.Qfill[P.Sj[q]] : P.Sj[q]);
         }
-    std::vector<int> acp((size_t)n + 1, 0), arp((size_t)m + 1, 0), arj((size_t)std::max(1L, anz)), arq((size_t)std::max(1L, anz));
-    for (long p = 0; p < anz; p++) { acp[(size_t)acol[(size_t)p] + 1]++; arp[(size_t)arow[(size_t)p] + 1]++; }
+    std::vector<int> acp((size_t)n + 1, 0), arp, arj, arq;
+    for (long p = 0; p < anz; p++) acp[(size_t)acol[(size_t)p] + 1]++;
     for (long j = 0; j < n; j++) acp[(size_t)j + 1] += acp[(size_t)j];
-    for (long i = 0; i < m; i++) arp[(size_t)i + 1] += arp[(size_t)i];
-    std::vector<int> next(arp.begin(), arp.end() - 1);
-    for (long p = 0; p < anz; p++) {                         // (A's order: column by column, so every row in column order)
-        const int q = next[(size_t)arow[(size_t)p]]++;
-        arj[(size_t)q] = acol[(size_t)p]; arq[(size_t)q] = (int)p;
-    }
-    LCHK(P.d_Acp.upload(acp, P.stream)); LCHK(P.d_Aci.upload(arow, P.stream));
-    LCHK(P.d_Arp.upload(arp, P.stream)); LCHK(P.d_Arj.upload(arj, P.stream)); LCHK(P.d_Arq.upload(arq, P.stream));
+    stm_row_form(m, anz, arow.data(), acol.data(), arp, arj, arq);      // (A's order: column by column, so every row in column order)
+    LCHK(P.a_idx.cp.upload(acp, P.stream)); LCHK(P.a_idx.ci.upload(arow, P.stream));
+    LCHK(P.a_idx.rp.upload(arp, P.stream)); LCHK(P.a_idx.rj.upload(arj, P.stream)); LCHK(P.a_idx.rq.upload(arq, P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));
     P.a_index_ready = true;
     return 0;

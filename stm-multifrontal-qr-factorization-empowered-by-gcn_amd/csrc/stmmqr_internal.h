@@ -3,6 +3,10 @@
 #pragma once
 #include "../../include/stmmqr_hip.h"
 
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
 extern "C" {
 // record the thread's last error (stmmqr_last_error) and return `code`
 int stm_fail(int code, const char *msg);
@@ -24,4 +28,32 @@ int stm_sparseqr_order(int ordering, double tol, stm_long m, stm_long n, const s
                        const stm_long *Quser, stm_long *Q);
 // m, n of a factorized SparseQR object (stmmqr_sparseqr.cpp)
 int stm_sparseqr_dims(const stmmqr_qr *qr, stm_long *m, stm_long *n);
+}
+
+// Row form of a sparse matrix from its nz entries in storage order (row[p], col[p]): rp [m + 1], and row by row the entries' columns
+// rj and storage positions rq.  A stable counting sort: within a row the entries keep their storage order, which fixes the order
+// in which k_spmv sums a row of A x.
+inline void stm_row_form(long m, long nz, const int *row, const int *col, std::vector<int> &rp, std::vector<int> &rj, std::vector<int> &rq)
+{
+    rp.assign((size_t)m + 1, 0);
+    rj.assign((size_t)std::max(1L, nz), 0); rq.assign((size_t)std::max(1L, nz), 0);
+    for (long p = 0; p < nz; p++) rp[(size_t)row[p] + 1]++;
+    for (long i = 0; i < m; i++) rp[(size_t)i + 1] += rp[(size_t)i];
+    std::vector<int> next(rp.begin(), rp.end() - 1);
+    for (long p = 0; p < nz; p++) {
+        const int q = next[(size_t)row[p]]++;
+        rj[(size_t)q] = col[p]; rq[(size_t)q] = (int)p;
+    }
+}
+
+// What the seminormal solves report: max over the right-hand sides of |A'r| / (|A|_F (|A|_F |x| + |b|)), from |A|_F = af and the
+// SQUARED norms zz = |A'r|^2, xx = |x|^2, bb = |b|^2 per right-hand side (0 / 0 counts as 0, q / 0 as infinity)
+inline double stm_seminormal_info(double af, const double *zz, const double *xx, const double *bb, long nrhs)
+{
+    double worst = 0;
+    for (long j = 0; j < nrhs; j++) {
+        const double den = af * (af * std::sqrt(xx[j]) + std::sqrt(bb[j])), q = std::sqrt(zz[j]);
+        worst = std::max(worst, den > 0 ? q / den : (q > 0 ? INFINITY : 0.0));
+    }
+    return worst;
 }

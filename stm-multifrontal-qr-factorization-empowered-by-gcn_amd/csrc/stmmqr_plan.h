@@ -83,6 +83,10 @@ template <class T> struct DevBuf {
     ~DevBuf() { release(); }
 };
 
+// What k_spmv reads of a sparse matrix A besides its values: the column form (cp, ci) for A'x and a row form (rp; per entry its
+// column rj and the position rq of its value in A's storage) for A x.  Built on the host by stm_row_form (stmmqr_internal.h).
+struct AIndexDev { DevBuf<int> cp, ci, rp, rj, rq; };
+
 struct Level {                           // tree level of a group: what the solve / Q-apply kernels walk (f1)
     int all_off = 0, n_all = 0;          // every front of the level (small first, then big by npanels desc)
     int n_small = 0, n_big = 0;
@@ -210,9 +214,8 @@ struct stmmqr_plan {
     DevBuf<unsigned long long> d_dbg, d_amax;
     DevBuf<double> d_sig;                           // {sg, 1/sg}: magnitude guard of the panel kernels
     DevBuf<char> d_Rdead;
-    // products with A on the device (stmmqr_plan_spmv, the seminormal solve): A's column form and a row form whose entries point
-    // at A's values (d_Ax), built at the first such call after set_pattern (stm_ensure_a_index)
-    DevBuf<int> d_Acp, d_Aci, d_Arp, d_Arj, d_Arq;
+    // products with A on the device (stmmqr_plan_spmv, the seminormal solve): built at the first such call after set_pattern (stm_ensure_a_index)
+    AIndexDev a_idx;
     std::vector<int> h_smap;                    // host copy of d_smap (what those forms are built from)
     bool a_index_ready = false;
     DevBuf<double> d_csB, d_csX, d_csR, d_csZ, d_csY, d_csD, d_csN;   // the seminormal solve's vectors (grown on demand)
@@ -279,7 +282,7 @@ struct stmmqr_plan {
         add(d_Stair); add(d_Hii); add(d_Cmap); add(d_Cursor); add(d_lists); add(d_smap); add(d_Rhoff); add(d_wlists);
         add(d_wcnt); add(d_wcnt2); add(d_wflag); add(d_wflag2); add(d_Rboff); add(d_Rdead); add(d_Ypend); add(d_ypoff);
         add(d_rhtop); add(d_fin); add(d_kept); add(d_scr); add(d_bounce); add(d_fs_scr);
-        add(d_Acp); add(d_Aci); add(d_Arp); add(d_Arj); add(d_Arq);
+        add(a_idx.cp); add(a_idx.ci); add(a_idx.rp); add(a_idx.rj); add(a_idx.rq);
         add(d_fs_car); add(d_fnum_car); add(d_carlist); add(d_carN);
         return b;
     }

@@ -1,183 +1,42 @@
 // stmmqr_rfactor.cpp -- SURVEY.md 8 (f1): QR_qmult / QR_solve on the factors resident in HBM (host side; kernels: stmmqr_resident.hip).
 #include "stmmqr_plan.h"
 #include <climits>
-
-extern "C" {
+#include <memory>
 
 // ---------------------------------------------------------------------------------------------
 // QR_qmult (SparseQR.c:1790-2020, methods QR_QTX / QR_QX) and QR_solve (RETX_EQUALS_B, :2024-2216)
 // on the factors that are still in HBM -- no download of the packed R+H.
 // ---------------------------------------------------------------------------------------------
 namespace {
-// host half of qr_hpinv for the device: Wmap[S-row id] = position in the permuted row order (same rule as in
-// stmmqr_plan_download); uploaded once per factorization together with the static maps
-int ensure_scratch(stmmqr_plan &P);
-int ensure_rowmap(stmmqr_plan &P)
-{
-    LCHK(ensure_scratch(P));
-    if (P.rowmap_ready) return 0;
-    hipStream_t st = P.stream;
-    const long nf = P.nf, m = P.m, n = P.n;
-    for (long f = 0; f < nf; f++)
-        if (P.group[f] < 0) return fail(STMMQR_ERR_INVALID, "Q-apply / solve need every front on this device");
-    std::vector<int> hii32((size_t)std::max(1L, P.hisize));
-    if (P.hisize > 0)
-        HIPCHK(hipMemcpyAsync(hii32.data(), P.d_Hii.p, (size_t)P.hisize * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (P.h_fnum.size() != (size_t)nf) P.h_fnum.resize((size_t)nf);
-    if (nf > 0)
-        HIPCHK(hipMemcpyAsync(P.h_fnum.data(), P.d_fnum.p, (size_t)nf * sizeof(FrontNum), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<int> W((size_t)std::max(1L, m), 0);
-    long row1 = 0, row2 = m;
-    for (long i = P.Sleft[n]; i < m; i++) W[i] = (int)--row2;
-    for (long f = 0; f < nf; f++) {
-        const int *Hi = hii32.data() + P.Hip[f];
-        const FrontNum &nm = P.h_fnum[f];
-        const long rm = nm.rank, fm = nm.fm;
-        for (long i = 0; i < rm; i++) W[Hi[i]] = (int)row1++;
-        const long cn = P.fs[f].fn - P.fs[f].fp;
-        const long cm = std::min(fm - rm, cn);
-        for (long i = fm - 1; i >= rm + cm; i--) W[Hi[i]] = (int)--row2;
-    }
-    LCHK(P.d_Wmap.upload(W, st));
-    {
-        std::vector<int> rb((size_t)std::max(1L, nf), 0);
-        long run = 0;
-        for (long f = 0; f < nf; f++) { rb[f] = (int)run; run += P.h_fnum[f].rank; }
-        LCHK(P.d_rowbase.upload(rb, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    if (!P.d_Rj.p) {
-        std::vector<int> t((size_t)std::max(1L, P.rjsize));
-        for (long i = 0; i < P.rjsize; i++) t[i] = (int)P.Rj[i];
-        LCHK(P.d_Rj.upload(t, st));
-        HIPCHK(hipStreamSynchronize(st));
-        t.assign((size_t)std::max(1L, m), 0);
-        for (long i = 0; i < m; i++) t[i] = (int)P.PLinv[i];
-        LCHK(P.d_PLinv.upload(t, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (P.has_qfill) {
-            t.assign((size_t)std::max(1L, n), 0);
-            for (long j = 0; j < n; j++) t[j] = (int)P.Qfill[j];
-            LCHK(P.d_Qfill.upload(t, st));
-            HIPCHK(hipStreamSynchronize(st));
-        }
-        LCHK(P.d_W.alloc((size_t)std::max(1L, m)));
-        LCHK(P.d_Xs.alloc((size_t)std::max(1L, n)));
-        LCHK(P.d_Io.alloc((size_t)std::max(1L, std::max(m, n))));
-        LCHK(P.d_err.alloc(1));
-        // dynamic LDS per level: k_qapply holds fm doubles + fn ints, k_rsolve fp + (fn - fp) doubles
-        const auto &LV = P.glevels[0];
-        P.level_lds_qa.assign(LV.size(), 0);
-        P.level_lds_qa_all.assign(LV.size(), 0);
-        P.level_lds_rs.assign(LV.size(), 0);
-        P.level_lds_rt.assign(LV.size(), 0);
-        P.level_qbig.assign(LV.size(), stmmqr_plan::QbLevel());
-        P.t4items.clear(); P.t4fronts.clear(); P.t4dqo.clear(); P.qbt4off.clear();
-        P.t4_doubles = 0; P.dq4_ints = 0; P.t4_ok = false; P.t4_tried = false; P.t4_valid = false;
-        std::vector<QbDesc> qb;
-        long xf = 1, dq = 1, wq = 1;
-        for (size_t l = 0; l < LV.size(); l++) {
-            long xo = 0, dqo = 0, wo = 0;
-            P.level_qbig[l].off = (int)qb.size();
-            P.level_qbig[l].t4i_off = (int)P.t4items.size();
-            for (int q = 0; q < LV[l].n_all; q++) {
-                const int f = P.lists[LV[l].all_off + q];
-                const FrontSym &s = P.fs[f];
-                const int need = (int)std::min(stm_lds_qapply(s.fm_ub, s.fn), (long)INT_MAX);
-                P.level_lds_rt[l] = std::max(P.level_lds_rt[l], (int)((((s.fn + 1) & ~1) + ((std::min(s.fp, std::max(s.fm_ub, 1)) + 2) & ~1)) * 8 + s.fp * 4 + 32));
-                P.level_lds_qa_all[l] = std::max(P.level_lds_qa_all[l], need);
-                if (s.qbig) {
-                    QbDesc d;
-                    d.f = f; d.xoff = (int)xo; d.dqoff = (int)dqo; d.wqoff = (int)wo; d.nslab = (s.fm_ub + STM_QB_ROWS - 1) / STM_QB_ROWS; d.np_live = s.npanels;
-                    qb.push_back(d);
-                    {
-                        const int ngr = (s.npanels + 3) / 4;
-                        P.qbt4off.push_back(P.t4_doubles);
-                        P.t4fronts.push_back(f);
-                        P.t4dqo.push_back(P.dq4_ints);
-                        for (int g = 0; g < ngr; g++) {
-                            Qt4ItemHost it;
-                            it.f = f; it.g = g; it.off = P.t4_doubles + (long long)g * stm_qt4_doubles(); it.dqo = P.dq4_ints;
-                            P.t4items.push_back(it);
-                        }
-                        P.t4_doubles += (long long)ngr * stm_qt4_doubles();
-                        P.dq4_ints += s.fn;
-                    }
-                    xo += s.fm_ub; dqo += s.fn; wo += 2L * d.nslab * STM_NB;
-                    auto &Q = P.level_qbig[l];
-                    Q.n++; Q.max_np = std::max(Q.max_np, s.npanels); Q.max_nslab = std::max(Q.max_nslab, d.nslab);
-                    Q.max_fm = std::max(Q.max_fm, s.fm_ub);
-                    Q.max_rsteps = std::max(Q.max_rsteps, (std::min(s.fp, s.fm_ub) + 31) / 32);
-                } else {
-                    P.level_lds_qa[l] = std::max(P.level_lds_qa[l], need);
-                    P.level_lds_rs[l] = std::max(P.level_lds_rs[l], (int)std::min(stm_lds_rsolve(s.fp, s.fn), (long)INT_MAX));
-                }
-            }
-            P.level_qbig[l].t4i_n = (int)P.t4items.size() - P.level_qbig[l].t4i_off;
-            xf = std::max(xf, xo); dq = std::max(dq, dqo); wq = std::max(wq, wo);
-        }
-        LCHK(P.d_Xf.alloc((size_t)xf));
-        LCHK(P.d_Dq.alloc((size_t)dq));
-        LCHK(P.d_Wq.alloc((size_t)wq));
-        P.wq4_doubles = 4 * wq;
-        P.xf_doubles = xf; P.wq_doubles = wq; P.rhs_cap = 1;
-        P.d_U.release(); P.d_Xr.release();
-        if (qb.empty()) qb.push_back(QbDesc());
-        LCHK(P.d_qb.alloc(qb.size()));
-        LCHK(P.d_Rm.alloc(qb.size()));
-        HIPCHK(hipMemcpy(P.d_qb.p, qb.data(), qb.size() * sizeof(QbDesc), hipMemcpyHostToDevice));
-        P.h_qb = qb;
-    }
-    {
-        // Of THIS factorization: the panels of a split front that can hold a live reflector and the blocks of live pivot columns.  A
-        // front of fm rows has fm live reflectors at most; they sit in its first fm + (dead pivot columns) columns, and a front has at
-        // most fp - rank dead pivot columns.  The panels behind that column were launches that did nothing: on the default workload
-        // 330 launches per Q'b, 177 of them for panels without a reflector (same finding as the factorization's own schedule,
-        // stmmqr_host.cpp "how many panels").  STMMQR_LIVE_PANELS=0: every panel.
-        const bool live = !(getenv("STMMQR_LIVE_PANELS") && atoi(getenv("STMMQR_LIVE_PANELS")) == 0);
-        bool changed = false;
-        for (size_t l = 0; l < P.level_qbig.size(); l++) {
-            auto &Q = P.level_qbig[l];
-            Q.live_np = 0; Q.live_rsteps = 0;
-            for (int q = 0; q < Q.n; q++) {
-                QbDesc &d = P.h_qb[(size_t)(Q.off + q)];
-                const FrontSym &s = P.fs[d.f];
-                const FrontNum &nm = P.h_fnum[d.f];
-                int npl = s.npanels;
-                if (live) {
-                    const long lastcol = std::min((long)s.fn, (long)nm.fm + std::max(0L, (long)s.fp - (long)nm.rank));
-                    npl = (nm.fm <= 0) ? 0 : (int)std::min((long)s.npanels, (lastcol - 1) / STM_NB + 1);
-                }
-                if (d.np_live != npl) { d.np_live = npl; changed = true; }
-                Q.live_np = std::max(Q.live_np, npl);
-                Q.live_rsteps = std::max(Q.live_rsteps, live ? (int)((nm.rank + 31) / 32) : Q.max_rsteps);
-            }
-        }
-        if (changed && !P.h_qb.empty()) HIPCHK(hipMemcpy(P.d_qb.p, P.h_qb.data(), P.h_qb.size() * sizeof(QbDesc), hipMemcpyHostToDevice));
-    }
-    // (the planner sends such fronts to the split kernels, so neither can happen; no launch may ask for more LDS than configured)
-    for (int b : P.level_lds_qa)
-        if (b > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front has more rows than the Q-apply kernel holds in LDS");
-    for (int b : P.level_lds_rs)
-        if (b > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front has more columns than the back-substitution kernel holds in LDS");
-    P.rowmap_ready = true;
-    return 0;
-}
-
-int check_device_err(stmmqr_plan &P, const char *what)
-{
-    int e = 0;
-    HIPCHK(hipMemcpyAsync(&e, P.d_err.p, sizeof(int), hipMemcpyDeviceToHost, P.stream));
-    HIPCHK(hipStreamSynchronize(P.stream));
-    if (e) return fail(STMMQR_ERR_INVALID, what);
-    return 0;
-}
+// a callee's own refusal goes up as it is (LCHK is for HIP error codes and would re-label it)
+#define PASS(expr) do { int e_ = (expr); if (e_ != 0) return e_; } while (0)
 
 // Slab recycling: the resident-factor kernels read fronts in front form.  A front whose slab was recycled is put back into
 // that form, level by level, in a scratch that holds the widest tree level (res_ctx: the FrontSym array whose offsets point into
 // the scratch; level_to_front_form: zeros + the inverse of k_rh_copy for the level's fronts).  Kept fronts are read where they are
 // (their offset is taken relative to the scratch's base: one flat device address space).
+// The FrontSym array those kernels read (host copy): fs, or with recycling fs_scr with the kept fronts rebased
+std::vector<FrontSym> resident_front_syms(const stmmqr_plan &P)
+{
+    if (!P.recycle) return P.fs;
+    std::vector<FrontSym> t = P.fs_scr;
+    for (long f = 0; f < P.nf; f++)
+        if (P.kept[(size_t)f]) t[(size_t)f].foff = (long long)((P.d_F.p + P.fs[f].foff) - P.d_scr.p);
+    return t;
+}
+// ... and who may cut that array back to a view that ends at column ncol of a plan of [A B] (the carried solve, the covariance): the
+// columns of A were rank-tested, those of B were not and sit where they were given
+int check_carried_view(const stmmqr_plan &P, long ncol)
+{
+    if (P.last_ntol != ncol)
+        return fail(STMMQR_ERR_INVALID, "carried solve: the factorization was made with ntol = " + std::to_string(P.last_ntol) + ", not n = " +
+                                            std::to_string(ncol) + " (the columns of B must not be rank-tested, those of A must)");
+    if (P.has_qfill)
+        for (long j = ncol; j < P.n; j++)
+            if (P.Qfill[(size_t)j] != j)
+                return fail(STMMQR_ERR_INVALID, "carried solve: column " + std::to_string(j) + " of [A B] is permuted (Qfill must be the identity on the B columns)");
+    return 0;
+}
 int ensure_scratch(stmmqr_plan &P)
 {
     if (!P.recycle || (P.d_scr.p && P.d_fs_scr.p)) return 0;
@@ -199,10 +58,7 @@ int ensure_scratch(stmmqr_plan &P)
     P.scr_valid = false;
     P.t4_valid = false;
     LCHK(P.d_scr.alloc((size_t)std::max(1LL, P.scr_all ? all : P.scr_doubles)));
-    std::vector<FrontSym> t = P.fs_scr;
-    for (long f = 0; f < P.nf; f++)
-        if (P.kept[(size_t)f]) t[(size_t)f].foff = (long long)((P.d_F.p + P.fs[f].foff) - P.d_scr.p);
-    LCHK(P.d_fs_scr.upload(t, P.stream));
+    LCHK(P.d_fs_scr.upload(resident_front_syms(P), P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));
     return 0;
 }
@@ -234,6 +90,189 @@ int level_to_front_form(stmmqr_plan &P, size_t l)
     return unpack_fronts(P, c, P.d_lists.p + LV[l].all_off, LV[l].n_all);
 }
 
+// Of THIS factorization: the host half of qr_hpinv for the device, Wmap[S-row id] = position in the permuted row order (same rule as
+// in stmmqr_plan_download), the rows of R above every front, and the host copy of the fronts' numeric results
+int map_rows_of_factorization(stmmqr_plan &P)
+{
+    hipStream_t st = P.stream;
+    const long nf = P.nf, m = P.m, n = P.n;
+    std::vector<int> hii32((size_t)std::max(1L, P.hisize));
+    if (P.hisize > 0)
+        HIPCHK(hipMemcpyAsync(hii32.data(), P.d_Hii.p, (size_t)P.hisize * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (P.h_fnum.size() != (size_t)nf) P.h_fnum.resize((size_t)nf);
+    if (nf > 0)
+        HIPCHK(hipMemcpyAsync(P.h_fnum.data(), P.d_fnum.p, (size_t)nf * sizeof(FrontNum), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int> W((size_t)std::max(1L, m), 0);
+    long row1 = 0, row2 = m;
+    for (long i = P.Sleft[n]; i < m; i++) W[i] = (int)--row2;
+    for (long f = 0; f < nf; f++) {
+        const int *Hi = hii32.data() + P.Hip[f];
+        const FrontNum &nm = P.h_fnum[f];
+        const long rm = nm.rank, fm = nm.fm;
+        for (long i = 0; i < rm; i++) W[Hi[i]] = (int)row1++;
+        const long cn = P.fs[f].fn - P.fs[f].fp;
+        const long cm = std::min(fm - rm, cn);
+        for (long i = fm - 1; i >= rm + cm; i--) W[Hi[i]] = (int)--row2;
+    }
+    LCHK(P.d_Wmap.upload(W, st));
+    std::vector<int> rb((size_t)std::max(1L, nf), 0);
+    long run = 0;
+    for (long f = 0; f < nf; f++) { rb[f] = (int)run; run += P.h_fnum[f].rank; }
+    LCHK(P.d_rowbase.upload(rb, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Once per plan: the static integer maps, the work vectors for one right-hand side, the dynamic LDS of every tree level's launches
+// (stm_lds_*, stmmqr_device.h), the descriptors of the split fronts and the bookkeeping of their grouped Q-apply (T4)
+int build_resident_tables(stmmqr_plan &P)
+{
+    hipStream_t st = P.stream;
+    const long m = P.m, n = P.n;
+    std::vector<int> t((size_t)std::max(1L, P.rjsize));
+    for (long i = 0; i < P.rjsize; i++) t[i] = (int)P.Rj[i];
+    LCHK(P.d_Rj.upload(t, st));
+    HIPCHK(hipStreamSynchronize(st));
+    t.assign((size_t)std::max(1L, m), 0);
+    for (long i = 0; i < m; i++) t[i] = (int)P.PLinv[i];
+    LCHK(P.d_PLinv.upload(t, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (P.has_qfill) {
+        t.assign((size_t)std::max(1L, n), 0);
+        for (long j = 0; j < n; j++) t[j] = (int)P.Qfill[j];
+        LCHK(P.d_Qfill.upload(t, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    LCHK(P.d_W.alloc((size_t)std::max(1L, m)));
+    LCHK(P.d_Xs.alloc((size_t)std::max(1L, n)));
+    LCHK(P.d_Io.alloc((size_t)std::max(1L, std::max(m, n))));
+    LCHK(P.d_err.alloc(1));
+    const auto &LV = P.glevels[0];
+    P.level_lds_qa.assign(LV.size(), 0);
+    P.level_lds_qa_all.assign(LV.size(), 0);
+    P.level_lds_rs.assign(LV.size(), 0);
+    P.level_lds_rt.assign(LV.size(), 0);
+    P.level_qbig.assign(LV.size(), stmmqr_plan::QbLevel());
+    P.t4items.clear(); P.t4fronts.clear(); P.t4dqo.clear(); P.qbt4off.clear();
+    P.t4_doubles = 0; P.dq4_ints = 0; P.t4_ok = false; P.t4_tried = false; P.t4_valid = false;
+    std::vector<QbDesc> qb;
+    long xf = 1, dq = 1, wq = 1;
+    for (size_t l = 0; l < LV.size(); l++) {
+        long xo = 0, dqo = 0, wo = 0;
+        P.level_qbig[l].off = (int)qb.size();
+        P.level_qbig[l].t4i_off = (int)P.t4items.size();
+        for (int q = 0; q < LV[l].n_all; q++) {
+            const int f = P.lists[LV[l].all_off + q];
+            const FrontSym &s = P.fs[f];
+            const int need = (int)std::min(stm_lds_qapply(s.fm_ub, s.fn), (long)INT_MAX);
+            P.level_lds_rt[l] = std::max(P.level_lds_rt[l], (int)std::min(stm_lds_rtsolve(s.fp, s.fm_ub, s.fn), (long)INT_MAX));
+            P.level_lds_qa_all[l] = std::max(P.level_lds_qa_all[l], need);
+            if (s.qbig) {
+                QbDesc d;
+                d.f = f; d.xoff = (int)xo; d.dqoff = (int)dqo; d.wqoff = (int)wo; d.nslab = (s.fm_ub + STM_QB_ROWS - 1) / STM_QB_ROWS; d.np_live = s.npanels;
+                qb.push_back(d);
+                const int ngr = (s.npanels + 3) / 4;
+                P.qbt4off.push_back(P.t4_doubles);
+                P.t4fronts.push_back(f);
+                P.t4dqo.push_back(P.dq4_ints);
+                for (int g = 0; g < ngr; g++) {
+                    Qt4ItemHost it;
+                    it.f = f; it.g = g; it.off = P.t4_doubles + (long long)g * stm_qt4_doubles(); it.dqo = P.dq4_ints;
+                    P.t4items.push_back(it);
+                }
+                P.t4_doubles += (long long)ngr * stm_qt4_doubles();
+                P.dq4_ints += s.fn;
+                xo += s.fm_ub; dqo += s.fn; wo += 2L * d.nslab * STM_NB;
+                auto &Q = P.level_qbig[l];
+                Q.n++; Q.max_np = std::max(Q.max_np, s.npanels); Q.max_nslab = std::max(Q.max_nslab, d.nslab);
+                Q.max_fm = std::max(Q.max_fm, s.fm_ub);
+                Q.max_rsteps = std::max(Q.max_rsteps, (std::min(s.fp, s.fm_ub) + 31) / 32);
+            } else {
+                P.level_lds_qa[l] = std::max(P.level_lds_qa[l], need);
+                P.level_lds_rs[l] = std::max(P.level_lds_rs[l], (int)std::min(stm_lds_rsolve(s.fp, s.fn), (long)INT_MAX));
+            }
+        }
+        P.level_qbig[l].t4i_n = (int)P.t4items.size() - P.level_qbig[l].t4i_off;
+        xf = std::max(xf, xo); dq = std::max(dq, dqo); wq = std::max(wq, wo);
+    }
+    LCHK(P.d_Xf.alloc((size_t)xf));
+    LCHK(P.d_Dq.alloc((size_t)dq));
+    LCHK(P.d_Wq.alloc((size_t)wq));
+    P.wq4_doubles = 4 * wq;
+    P.xf_doubles = xf; P.wq_doubles = wq; P.rhs_cap = 1;
+    P.d_U.release(); P.d_Xr.release();
+    if (qb.empty()) qb.push_back(QbDesc());
+    LCHK(P.d_qb.alloc(qb.size()));
+    LCHK(P.d_Rm.alloc(qb.size()));
+    HIPCHK(hipMemcpy(P.d_qb.p, qb.data(), qb.size() * sizeof(QbDesc), hipMemcpyHostToDevice));
+    P.h_qb = qb;
+    return 0;
+}
+
+// Of THIS factorization: the panels of a split front that can hold a live reflector and the blocks of live pivot columns.  A
+// front of fm rows has fm live reflectors at most; they sit in its first fm + (dead pivot columns) columns, and a front has at
+// most fp - rank dead pivot columns.  The panels behind that column were launches that did nothing: on the default workload
+// 330 launches per Q'b, 177 of them for panels without a reflector (same finding as the factorization's own schedule,
+// stmmqr_host.cpp "how many panels").  STMMQR_LIVE_PANELS=0: every panel.
+int count_live_panels(stmmqr_plan &P)
+{
+    const bool live = !(getenv("STMMQR_LIVE_PANELS") && atoi(getenv("STMMQR_LIVE_PANELS")) == 0);
+    bool changed = false;
+    for (size_t l = 0; l < P.level_qbig.size(); l++) {
+        auto &Q = P.level_qbig[l];
+        Q.live_np = 0; Q.live_rsteps = 0;
+        for (int q = 0; q < Q.n; q++) {
+            QbDesc &d = P.h_qb[(size_t)(Q.off + q)];
+            const FrontSym &s = P.fs[d.f];
+            const FrontNum &nm = P.h_fnum[d.f];
+            int npl = s.npanels;
+            if (live) {
+                const long lastcol = std::min((long)s.fn, (long)nm.fm + std::max(0L, (long)s.fp - (long)nm.rank));
+                npl = (nm.fm <= 0) ? 0 : (int)std::min((long)s.npanels, (lastcol - 1) / STM_NB + 1);
+            }
+            if (d.np_live != npl) { d.np_live = npl; changed = true; }
+            Q.live_np = std::max(Q.live_np, npl);
+            Q.live_rsteps = std::max(Q.live_rsteps, live ? (int)((nm.rank + 31) / 32) : Q.max_rsteps);
+        }
+    }
+    if (changed && !P.h_qb.empty()) HIPCHK(hipMemcpy(P.d_qb.p, P.h_qb.data(), P.h_qb.size() * sizeof(QbDesc), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// what every resident-factor operation needs of the plan and of the factorization it holds, built at the first one after a factorization
+int ensure_rowmap(stmmqr_plan &P)
+{
+    LCHK(ensure_scratch(P));
+    if (P.rowmap_ready) return 0;
+    for (long f = 0; f < P.nf; f++)
+        if (P.group[f] < 0) return fail(STMMQR_ERR_INVALID, "Q-apply / solve need every front on this device");
+    PASS(map_rows_of_factorization(P));
+    if (!P.d_Rj.p) PASS(build_resident_tables(P));
+    PASS(count_live_panels(P));
+    // (the planner sends such fronts to the split kernels, so neither can happen; no launch may ask for more LDS than configured)
+    for (int b : P.level_lds_qa)
+        if (b > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front has more rows than the Q-apply kernel holds in LDS");
+    for (int b : P.level_lds_rs)
+        if (b > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front has more columns than the back-substitution kernel holds in LDS");
+    P.rowmap_ready = true;
+    return 0;
+}
+
+// How every entry point starts and ends: the refusal that comes before it looks at its other arguments; once they are accepted, the
+// plan's device and the maps of the factorization held; and, where it cleared the kernels' error word d_err on its way (the Q-apply
+// alone does not), the check of that word, which synchronizes the stream.
+int check_factored(const stmmqr_plan *plan) { return (plan && plan->factored) ? 0 : fail(STMMQR_ERR_INVALID, "no factorization held by the plan"); }
+int begin_resident_op(stmmqr_plan &P) { HIPCHK(hipSetDevice(P.device)); LCHK(ensure_rowmap(P)); return 0; }
+int end_resident_op(stmmqr_plan &P)
+{
+    int e = 0;
+    HIPCHK(hipMemcpyAsync(&e, P.d_err.p, sizeof(int), hipMemcpyDeviceToHost, P.stream));
+    HIPCHK(hipStreamSynchronize(P.stream));
+    if (e) return fail(STMMQR_ERR_INVALID, "internal: live pivot count of a front differs from its rank");
+    return 0;
+}
+
 // the per-vector buffers of the resident-factor operations for a batch of nb right-hand sides (grown on demand, never shrunk)
 int ensure_rhs_batch(stmmqr_plan &P, int nb)
 {
@@ -260,6 +299,17 @@ int rhs_batch_max()
     static int v = -1;
     if (v < 0) v = getenv("STMMQR_RHS_BATCH") ? std::max(1, atoi(getenv("STMMQR_RHS_BATCH"))) : 32;
     return v;
+}
+// op(j0, nb) for the right-hand sides j0 .. j0 + nb - 1, batch after batch: every launch of a pass over the tree carries a whole batch
+// (RhsBatch), and the per-vector buffers hold it before op runs
+template <class Op> int for_each_batch(stmmqr_plan &P, stm_long nrhs, Op op)
+{
+    for (stm_long j0 = 0; j0 < nrhs; j0 += rhs_batch_max()) {
+        const int nb = (int)std::min<stm_long>(rhs_batch_max(), nrhs - j0);
+        LCHK(ensure_rhs_batch(P, nb));
+        PASS(op(j0, nb));
+    }
+    return 0;
 }
 
 // W (device, S-row order; nb vectors at stride m) <- Q' W or Q W
@@ -316,7 +366,7 @@ int run_qapply(stmmqr_plan &P, int method, int nb = 1)
                                        P.d_Wq.p, P.stream, nb, B));
             return 0;
         }
-        if (P.level_lds_qa_all[l] > 131072) return fail(STMMQR_ERR_TOO_LARGE, "a front has more rows than the unblocked Q-apply kernel holds in LDS");
+        if (P.level_lds_qa_all[l] > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front has more rows than the unblocked Q-apply kernel holds in LDS");
         for (int j = 0; j < nb; j++)                                  // (the reflector-by-reflector cross-check kernel: one vector per launch)
             LCHK(stm_launch_qapply(c, L0 + LV[l].all_off, LV[l].n_all, m, P.d_W.p + (size_t)j * (size_t)P.m, P.level_lds_qa_all[l], P.d_err.p, P.stream));
         return 0;
@@ -328,58 +378,106 @@ int run_qapply(stmmqr_plan &P, int method, int nb = 1)
     }
     return 0;
 }
-}  // namespace
 
-namespace {
-// host matrix (rows x cols, leading dimension ld) <-> contiguous device matrix (rows x cols), one transfer each way
-int upload_cols(stmmqr_plan &P, DevBuf<double> &d, const double *H, long ld, long rows, long cols)
+// rows x cols doubles from one column-major array (leading dimension lds) to another (ldd), host or device by `kind`: one transfer
+int copy_cols(double *dst, long ldd, const double *src, long lds, long rows, long cols, hipMemcpyKind kind, hipStream_t st)
 {
-    if ((size_t)(rows * cols) > d.n) LCHK(d.alloc((size_t)std::max(1L, rows * cols)));
     if (rows > 0 && cols > 0)
-        HIPCHK(hipMemcpy2DAsync(d.p, (size_t)rows * sizeof(double), H, (size_t)ld * sizeof(double), (size_t)rows * sizeof(double),
-                                (size_t)cols, hipMemcpyHostToDevice, P.stream));
+        HIPCHK(hipMemcpy2DAsync(dst, (size_t)ldd * sizeof(double), src, (size_t)lds * sizeof(double), (size_t)rows * sizeof(double), (size_t)cols,
+                                kind, st));
     return 0;
 }
-int download_cols(stmmqr_plan &P, const DevBuf<double> &d, double *H, long ld, long rows, long cols)
+int grow(DevBuf<double> &d, size_t n) { return (d.p && d.n >= n) ? 0 : d.alloc(std::max<size_t>(n, 1)); }
+// ... from the host into a device buffer that holds the columns one after the other and is grown if needed
+int upload_cols(DevBuf<double> &d, const double *H, long ld, long rows, long cols, hipStream_t st)
 {
-    if (rows > 0 && cols > 0)
-        HIPCHK(hipMemcpy2DAsync(H, (size_t)ld * sizeof(double), d.p, (size_t)rows * sizeof(double), (size_t)rows * sizeof(double),
-                                (size_t)cols, hipMemcpyDeviceToHost, P.stream));
+    LCHK(grow(d, (size_t)(rows * cols)));
+    return copy_cols(d.p, rows, H, ld, rows, cols, hipMemcpyHostToDevice, st);
+}
+// ... and back out of such a buffer (to the host, or with `kind` to a caller's device array); waits for it
+int download_cols(stmmqr_plan &P, const DevBuf<double> &d, double *H, long ld, long rows, long cols, hipMemcpyKind kind = hipMemcpyDeviceToHost)
+{
+    PASS(copy_cols(H, ld, d.p, rows, rows, cols, kind, P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));
     return 0;
 }
+
 // nb vectors (stride m in `in` / `out`, device, the reference's row order) through Q' (method 0) or Q (method 1) in ONE pass over the tree
 int qapply_vectors(stmmqr_plan &P, int method, const double *in, double *out, int nb)
 {
-    hipStream_t st = P.stream;
-    const int m = (int)P.m;
-    LCHK(ensure_rhs_batch(P, nb));
-    if (method == 0) {
-        LCHK(stm_launch_perm(in, P.d_PLinv.p, P.d_W.p, m, 1, st, nb, m, m));            // W[PLinv[i]] = x[i]
-        LCHK(run_qapply(P, 0, nb));
-        LCHK(stm_launch_perm(P.d_W.p, P.d_Wmap.p, out, m, 1, st, nb, m, m));            // out[Wmap[r]] = W[r]
-    } else {
-        LCHK(stm_launch_perm(in, P.d_Wmap.p, P.d_W.p, m, 0, st, nb, m, m));             // W[r] = x[Wmap[r]]
-        LCHK(run_qapply(P, 1, nb));
-        LCHK(stm_launch_perm(P.d_W.p, P.d_PLinv.p, out, m, 0, st, nb, m, m));           // out[i] = W[PLinv[i]]
+    const int m = (int)P.m, scatter = method == 0;
+    // Q': W[PLinv[i]] = x[i], then out[Wmap[r]] = W[r];  Q: W[r] = x[Wmap[r]], then out[i] = W[PLinv[i]]
+    LCHK(stm_launch_perm(in, scatter ? P.d_PLinv.p : P.d_Wmap.p, P.d_W.p, m, scatter, P.stream, nb, m, m));
+    LCHK(run_qapply(P, method, nb));
+    LCHK(stm_launch_perm(P.d_W.p, scatter ? P.d_Wmap.p : P.d_PLinv.p, out, m, scatter, P.stream, nb, m, m));
+    return 0;
+}
+
+// The backward pass, R x = y, from the root to the leaves: y in the device work vectors W (internal row order; nb of them at stride
+// m) -> d_Xs (R's column order, stride n).  The kernels read the factorization through c; before_level(l), a launch of the caller's
+// or nothing (it returns the launcher's code), comes once the level is in front form, before its solves.
+template <class Hook> int r_pass(stmmqr_plan &P, const DevCtx &c, int nb, Hook before_level)
+{
+    const RhsBatch B = rhs_strides(P);
+    const int *L0 = P.d_lists.p;
+    const auto &LV = P.glevels[0];
+    for (size_t l = LV.size(); l-- > 0;) {
+        LCHK(level_to_front_form(P, l));
+        LCHK(before_level(l));
+        LCHK(stm_launch_rsolve(c, L0 + LV[l].all_off, LV[l].n_all, P.d_Rj.p, P.d_W.p, P.d_Xs.p, P.level_lds_rs[l], P.d_err.p, P.stream, nb, B));
+        const auto &Q = P.level_qbig[l];         // the large fronts of the level: rows split over workgroups
+        LCHK(stm_launch_rsolve_big(c, P.d_qb.p + Q.off, Q.n, Q.live_rsteps, Q.max_nslab, P.d_Rj.p, P.d_W.p, P.d_Xs.p, P.d_Xf.p,
+                                   P.d_Dq.p, P.d_Rm.p + Q.off, P.d_err.p, P.stream, nb, B));
     }
     return 0;
 }
-// back substitution R x = y on the device work vectors W (internal row order; nb of them at stride m) -> d_Xs (R's column order, stride n)
-int rsolve_vector(stmmqr_plan &P, int nb = 1)
+int rsolve_vector(stmmqr_plan &P, int nb = 1) { return r_pass(P, res_ctx(P), nb, [](size_t) { return 0; }); }
+// nb vectors Y (device, stride m, R's row order) -> X (device, stride n) = R \ Y or, through Qfill, E (R \ Y): stmmqr_plan_rsolve 0, 1
+int r_vectors(stmmqr_plan &P, const double *Y, double *X, int nb, bool through_qfill)
+{
+    hipStream_t st = P.stream;
+    const long m = P.m, n = P.n;
+    LCHK(stm_launch_perm(Y, P.d_Wmap.p, P.d_W.p, (int)m, 0, st, nb, m, m));                                  // W[r] = y[Wmap[r]]
+    LCHK(rsolve_vector(P, nb));
+    LCHK(stm_launch_perm(P.d_Xs.p, (through_qfill && P.has_qfill) ? P.d_Qfill.p : nullptr, X, (int)n, 1, st, nb, n, n));   // X[Qfill[j]] = x[j]
+    return 0;
+}
+
+// The forward pass, R' x = b, from the leaves to the root: b in R's column order in d_Xs (nb vectors at stride n) -> d_Xr (R's row
+// order, stride m; rows beyond the rank stay zero).  ensure_rt comes before the first batch: it refuses a tree that k_rtsolve cannot
+// take and makes the pass's own buffers (U, Xr) at the plan's current batch size, from where ensure_rhs_batch grows them.
+int ensure_rt(stmmqr_plan &P)
+{
+    for (int need : P.level_lds_rt)
+        if (need > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front is too wide for the one-workgroup R' solve");
+    if (!P.d_U.p) {
+        LCHK(P.d_U.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, P.rjsize)));
+        LCHK(P.d_Xr.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, P.m)));
+    }
+    return 0;
+}
+int rt_pass(stmmqr_plan &P, int nb)
 {
     const RhsBatch B = rhs_strides(P);
     DevCtx c = res_ctx(P);
     const int *L0 = P.d_lists.p;
     const auto &LV = P.glevels[0];
-    hipStream_t st = P.stream;
-    for (size_t l = LV.size(); l-- > 0;) {
+    HIPCHK(hipMemsetAsync(P.d_Xr.p, 0, (size_t)nb * (size_t)std::max(1L, P.m) * sizeof(double), P.stream));
+    for (size_t l = 0; l < LV.size(); l++) {
         LCHK(level_to_front_form(P, l));
-        LCHK(stm_launch_rsolve(c, L0 + LV[l].all_off, LV[l].n_all, P.d_Rj.p, P.d_W.p, P.d_Xs.p, P.level_lds_rs[l], P.d_err.p, st, nb, B));
-        const auto &Q = P.level_qbig[l];         // the large fronts of the level: rows split over workgroups
-        LCHK(stm_launch_rsolve_big(c, P.d_qb.p + Q.off, Q.n, Q.live_rsteps, Q.max_nslab, P.d_Rj.p, P.d_W.p, P.d_Xs.p, P.d_Xf.p,
-                                   P.d_Dq.p, P.d_Rm.p + Q.off, P.d_err.p, st, nb, B));
+        LCHK(stm_launch_rtsolve(c, L0 + LV[l].all_off, LV[l].n_all, P.d_Xs.p, P.d_U.p, P.d_Xr.p, P.d_rowbase.p, P.level_lds_rt[l], P.stream, nb, B));
     }
+    return 0;
+}
+// nb vectors Z (device, stride n) -> Y (device, stride m) = R' \ Z or, through Qfill, R' \ (E' Z): stmmqr_plan_rsolve 2, 3
+int rt_vectors(stmmqr_plan &P, const double *Z, double *Y, int nb, bool through_qfill)
+{
+    hipStream_t st = P.stream;
+    const long m = P.m, n = P.n;
+    // b in R's column order: E'Z gathers through Qfill
+    LCHK(stm_launch_perm(Z, (through_qfill && P.has_qfill) ? P.d_Qfill.p : nullptr, P.d_Xs.p, (int)n, 0, st, nb, n, n));
+    LCHK(rt_pass(P, nb));
+    HIPCHK(hipMemcpyAsync(Y, P.d_Xr.p, (size_t)nb * (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
     return 0;
 }
 }  // namespace
@@ -391,36 +489,26 @@ int rsolve_vector(stmmqr_plan &P, int nb = 1)
 // factorization (HPinv), Q X and X Q' take it.  All vectors cross PCIe in ONE transfer each way.
 int stmmqr_plan_qmult(stmmqr_plan *plan, int method, double *X, stm_long ldx, stm_long k)
 {
-    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    PASS(check_factored(plan));
     if (!X || k < 0 || method < 0 || method > 3 || ldx < ((method <= 1) ? plan->m : k))
         return fail(STMMQR_ERR_INVALID, "bad qmult arguments");
     if (!plan->keep_h) return fail(STMMQR_ERR_INVALID, "the plan keeps no Householder vectors (keepH = 0): no Q-apply");
     stmmqr_plan &P = *plan;
-    HIPCHK(hipSetDevice(P.device));
-    LCHK(ensure_rowmap(P));
+    PASS(begin_resident_op(P));
     const long m = P.m;
     if (k == 0 || m == 0) return 0;
-    if (method <= 1) {
-        LCHK(upload_cols(P, P.d_Xall, X, ldx, m, k));
-        // (batches of right-hand sides: every launch of the pass over the tree carries all of them, RhsBatch)
-        for (stm_long j = 0; j < k; j += rhs_batch_max()) {
-            const int nb = (int)std::min<stm_long>(rhs_batch_max(), k - j);
-            LCHK(qapply_vectors(P, method, P.d_Xall.p + j * m, P.d_Xall.p + j * m, nb));
-        }
-        return download_cols(P, P.d_Xall, X, ldx, m, k);
-    }
     // X Q' = (Q X')' and X Q = (Q' X')': the rows of X are the vectors (SparseQR.c:2040-2075: the same permutation pattern)
-    std::vector<double> T((size_t)m * (size_t)k);
-    for (stm_long r = 0; r < k; r++)
+    const bool rows = method >= 2;
+    const int vm = rows ? (method == 2) : method;
+    std::vector<double> T(rows ? (size_t)m * (size_t)k : 0);
+    for (stm_long r = 0; r < k && rows; r++)
         for (long i = 0; i < m; i++) T[(size_t)r * m + i] = X[r + (size_t)i * ldx];
-    LCHK(upload_cols(P, P.d_Xall, T.data(), m, m, k));
-    const int vm = (method == 2) ? 1 : 0;
-    for (stm_long r = 0; r < k; r += rhs_batch_max()) {
-        const int nb = (int)std::min<stm_long>(rhs_batch_max(), k - r);
-        LCHK(qapply_vectors(P, vm, P.d_Xall.p + r * m, P.d_Xall.p + r * m, nb));
-    }
-    LCHK(download_cols(P, P.d_Xall, T.data(), m, m, k));
-    for (stm_long r = 0; r < k; r++)
+    double *H = rows ? T.data() : X;
+    const long ldh = rows ? m : ldx;
+    LCHK(upload_cols(P.d_Xall, H, ldh, m, k, P.stream));
+    PASS(for_each_batch(P, k, [&](stm_long j, int nb) { return qapply_vectors(P, vm, P.d_Xall.p + j * m, P.d_Xall.p + j * m, nb); }));
+    PASS(download_cols(P, P.d_Xall, H, ldh, m, k));
+    for (stm_long r = 0; r < k && rows; r++)
         for (long i = 0; i < m; i++) X[r + (size_t)i * ldx] = T[(size_t)r * m + i];
     return 0;
 }
@@ -433,55 +521,23 @@ int stmmqr_plan_qmult(stmmqr_plan *plan, int method, double *X, stm_long ldx, st
 // Dead pivot columns: x = 0 (systems 0, 1: the basic solution of qr_rsolve) / no equation (2, 3: the squeezed R).
 int stmmqr_plan_rsolve(stmmqr_plan *plan, int system, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs)
 {
-    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    PASS(check_factored(plan));
     if (system < 0 || system > 3 || !B || !X || nrhs < 0) return fail(STMMQR_ERR_INVALID, "bad solve arguments");
     stmmqr_plan &P = *plan;
-    const long m = P.m, n = P.n;
-    const long brows = (system <= 1) ? m : n, xrows = (system <= 1) ? n : m;
+    const long m = P.m, n = P.n, brows = (system <= 1) ? m : n, xrows = (system <= 1) ? n : m;
     if (ldb < brows || ldx < xrows) return fail(STMMQR_ERR_INVALID, "bad leading dimension");
-    HIPCHK(hipSetDevice(P.device));
-    LCHK(ensure_rowmap(P));
-    hipStream_t st = P.stream;
+    PASS(begin_resident_op(P));
     if (nrhs == 0) return 0;
-    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
-    LCHK(upload_cols(P, P.d_Xall, B, ldb, brows, nrhs));
-    if ((size_t)(xrows * nrhs) > P.d_Yall.n) LCHK(P.d_Yall.alloc((size_t)std::max(1L, xrows * nrhs)));
-    const int nbmax = rhs_batch_max();
-    const RhsBatch RB = rhs_strides(P);
-    if (system <= 1) {
-        for (stm_long j = 0; j < nrhs; j += nbmax) {
-            const int nb = (int)std::min<stm_long>(nbmax, nrhs - j);
-            LCHK(ensure_rhs_batch(P, nb));
-            LCHK(stm_launch_perm(P.d_Xall.p + j * m, P.d_Wmap.p, P.d_W.p, (int)m, 0, st, nb, m, m));          // W[r] = b[Wmap[r]]
-            LCHK(rsolve_vector(P, nb));
-            LCHK(stm_launch_perm(P.d_Xs.p, (system == 1 && P.has_qfill) ? P.d_Qfill.p : nullptr, P.d_Yall.p + j * n, (int)n, 1, st, nb, n, n));
-        }
-    } else {
-        DevCtx c = res_ctx(P);
-        const int *L0 = P.d_lists.p;
-        const auto &LV = P.glevels[0];
-        if (!P.d_U.p) {
-            LCHK(P.d_U.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, P.rjsize)));
-            LCHK(P.d_Xr.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, m)));
-        }
-        for (int need : P.level_lds_rt)
-            if (need > 131072) return fail(STMMQR_ERR_TOO_LARGE, "a front is too wide for the one-workgroup R' solve");
-        for (stm_long j = 0; j < nrhs; j += nbmax) {
-            const int nb = (int)std::min<stm_long>(nbmax, nrhs - j);
-            LCHK(ensure_rhs_batch(P, nb));
-            // b in R's column order: E'B gathers through Qfill
-            LCHK(stm_launch_perm(P.d_Xall.p + j * n, (system == 3 && P.has_qfill) ? P.d_Qfill.p : nullptr, P.d_Xs.p, (int)n, 0, st, nb, n, n));
-            HIPCHK(hipMemsetAsync(P.d_Xr.p, 0, (size_t)nb * (size_t)std::max(1L, m) * sizeof(double), st));
-            for (size_t l = 0; l < LV.size(); l++) {
-                LCHK(level_to_front_form(P, l));
-                LCHK(stm_launch_rtsolve(c, L0 + LV[l].all_off, LV[l].n_all, P.d_Xs.p, P.d_U.p, P.d_Xr.p, P.d_rowbase.p,
-                                        P.level_lds_rt[l], st, nb, RB));
-            }
-            HIPCHK(hipMemcpyAsync(P.d_Yall.p + j * m, P.d_Xr.p, (size_t)nb * (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-    }
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), P.stream));
+    LCHK(upload_cols(P.d_Xall, B, ldb, brows, nrhs, P.stream));
+    LCHK(grow(P.d_Yall, (size_t)(xrows * nrhs)));
+    if (system >= 2) PASS(ensure_rt(P));
+    PASS(for_each_batch(P, nrhs, [&](stm_long j, int nb) {
+        return system <= 1 ? r_vectors(P, P.d_Xall.p + j * m, P.d_Yall.p + j * n, nb, system == 1)
+                           : rt_vectors(P, P.d_Xall.p + j * n, P.d_Yall.p + j * m, nb, system == 3);
+    }));
     LCHK(download_cols(P, P.d_Yall, X, ldx, xrows, nrhs));
-    return check_device_err(P, "internal: live pivot count of a front differs from its rank");
+    return end_resident_op(P);
 }
 
 // X (n x nrhs, ldx >= n) = E * R^{-1} * (Q' B)(1:n)  for B (m x nrhs, ldb >= m): QR_qmult(QR_QTX) followed by
@@ -489,76 +545,50 @@ int stmmqr_plan_rsolve(stmmqr_plan *plan, int system, const double *B, stm_long 
 // dead columns get x = 0 (basic solution).
 int stmmqr_plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs)
 {
-    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    PASS(check_factored(plan));
     if (!B || !X || ldb < plan->m || ldx < plan->n || nrhs < 0) return fail(STMMQR_ERR_INVALID, "bad solve arguments");
     if (!plan->keep_h)
         return fail(STMMQR_ERR_INVALID, "the plan keeps no Householder vectors (keepH = 0): no Q'B; stmmqr_plan_solve_seminormal solves with R only");
     stmmqr_plan &P = *plan;
-    HIPCHK(hipSetDevice(P.device));
-    LCHK(ensure_rowmap(P));
+    PASS(begin_resident_op(P));
     hipStream_t st = P.stream;
     const long m = P.m, n = P.n;
     if (nrhs == 0) return 0;
-    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
-    LCHK(upload_cols(P, P.d_Xall, B, ldb, m, nrhs));
-    if ((size_t)(n * nrhs) > P.d_Yall.n) LCHK(P.d_Yall.alloc((size_t)std::max(1L, n * nrhs)));
-    for (stm_long j = 0; j < nrhs; j += rhs_batch_max()) {
-        const int nb = (int)std::min<stm_long>(rhs_batch_max(), nrhs - j);
-        LCHK(ensure_rhs_batch(P, nb));
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), P.stream));
+    LCHK(upload_cols(P.d_Xall, B, ldb, m, nrhs, st));
+    LCHK(grow(P.d_Yall, (size_t)(n * nrhs)));
+    PASS(for_each_batch(P, nrhs, [&](stm_long j, int nb) -> int {
         LCHK(stm_launch_perm(P.d_Xall.p + j * m, P.d_PLinv.p, P.d_W.p, (int)m, 1, st, nb, m, m));
         LCHK(run_qapply(P, 0, nb));
         LCHK(rsolve_vector(P, nb));
         LCHK(stm_launch_perm(P.d_Xs.p, P.has_qfill ? P.d_Qfill.p : nullptr, P.d_Yall.p + j * n, (int)n, 1, st, nb, n, n));   // X[Qfill[j]] = x[j]
-    }
+        return 0;
+    }));
     LCHK(download_cols(P, P.d_Yall, X, ldx, n, nrhs));
-    return check_device_err(P, "internal: live pivot count of a front differs from its rank");
+    return end_resident_op(P);
 }
 
 // ---- products with A and the corrected seminormal equations (factors with or without H) ----
 namespace {
-// nb vectors Z (device, stride n) -> Y (device, stride m) = R' \ (E' Z): the launches of stmmqr_plan_rsolve's system 3
-int rt_vectors(stmmqr_plan &P, const double *Z, double *Y, int nb)
+// Y = A X (trans 0: X n x nrhs, Y m x nrhs), A' X (trans 1: X m, Y n), or with B (trans 0 only) Y = B - A X for the m x n matrix with
+// index A and values Ax; device arrays
+int spmv(const AIndexDev &A, const double *Ax, long m, long n, int trans, const double *X, long long ldx, const double *B, long long ldb,
+         double *Y, long long ldy, long long nrhs, hipStream_t st)
 {
-    hipStream_t st = P.stream;
-    const long m = P.m, n = P.n;
-    LCHK(ensure_rhs_batch(P, nb));
-    const RhsBatch RB = rhs_strides(P);
-    DevCtx c = res_ctx(P);
-    const int *L0 = P.d_lists.p;
-    const auto &LV = P.glevels[0];
-    LCHK(stm_launch_perm(Z, P.has_qfill ? P.d_Qfill.p : nullptr, P.d_Xs.p, (int)n, 0, st, nb, n, n));
-    HIPCHK(hipMemsetAsync(P.d_Xr.p, 0, (size_t)nb * (size_t)std::max(1L, m) * sizeof(double), st));
-    for (size_t l = 0; l < LV.size(); l++) {
-        LCHK(level_to_front_form(P, l));
-        LCHK(stm_launch_rtsolve(c, L0 + LV[l].all_off, LV[l].n_all, P.d_Xs.p, P.d_U.p, P.d_Xr.p, P.d_rowbase.p, P.level_lds_rt[l], st, nb, RB));
-    }
-    HIPCHK(hipMemcpyAsync(Y, P.d_Xr.p, (size_t)nb * (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return 0;
+    if (trans) return stm_launch_spmv((int)n, A.cp.p, A.ci.p, nullptr, Ax, X, ldx, B, ldb, Y, ldy, nrhs, st);
+    return stm_launch_spmv((int)m, A.rp.p, A.rj.p, A.rq.p, Ax, X, ldx, B, ldb, Y, ldy, nrhs, st);
 }
-// nb vectors Y (device, stride m, R's row order) -> X (device, stride n) = E (R \ Y): stmmqr_plan_rsolve's system 1
-int r_vectors(stmmqr_plan &P, const double *Y, double *X, int nb)
-{
-    hipStream_t st = P.stream;
-    const long m = P.m, n = P.n;
-    LCHK(ensure_rhs_batch(P, nb));
-    LCHK(stm_launch_perm(Y, P.d_Wmap.p, P.d_W.p, (int)m, 0, st, nb, m, m));
-    LCHK(rsolve_vector(P, nb));
-    LCHK(stm_launch_perm(P.d_Xs.p, P.has_qfill ? P.d_Qfill.p : nullptr, X, (int)n, 1, st, nb, n, n));
-    return 0;
-}
-// Y = A X (trans 0: X n x nrhs, Y m x nrhs), A' X (trans 1: X m, Y n), or with B (trans 0 only) Y = B - A X; device arrays
+// ... for the plan's A with the values of the last factorization
 int spmv_dev(stmmqr_plan &P, int trans, const double *X, long long ldx, const double *B, long long ldb, double *Y, long long ldy, long long nrhs)
 {
-    if (trans) return stm_launch_spmv((int)P.n, P.d_Acp.p, P.d_Aci.p, nullptr, P.d_Ax.p, X, ldx, B, ldb, Y, ldy, nrhs, P.stream);
-    return stm_launch_spmv((int)P.m, P.d_Arp.p, P.d_Arj.p, P.d_Arq.p, P.d_Ax.p, X, ldx, B, ldb, Y, ldy, nrhs, P.stream);
+    return spmv(P.a_idx, P.d_Ax.p, P.m, P.n, trans, X, ldx, B, ldb, Y, ldy, nrhs, P.stream);
 }
-int grow(DevBuf<double> &d, size_t n) { return (d.p && d.n >= n) ? 0 : d.alloc(std::max<size_t>(n, 1)); }
 }  // namespace
 
 // Y = A X (trans 0) or A' X (trans 1) with the values of the last factorization; see include/stmmqr_hip.h
 int stmmqr_plan_spmv(stmmqr_plan *plan, int trans, const double *X, stm_long ldx, double *Y, stm_long ldy, stm_long nrhs, int on_device)
 {
-    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    PASS(check_factored(plan));
     stmmqr_plan &P = *plan;
     const long xr = trans ? P.m : P.n, yr = trans ? P.n : P.m;
     if (!X || !Y || nrhs < 0 || (trans != 0 && trans != 1) || ldx < xr || ldy < yr) return fail(STMMQR_ERR_INVALID, "bad spmv arguments");
@@ -571,9 +601,8 @@ int stmmqr_plan_spmv(stmmqr_plan *plan, int trans, const double *X, stm_long ldx
         HIPCHK(hipStreamSynchronize(P.stream));
         return 0;
     }
-    LCHK(grow(P.d_csX, (size_t)xr * (size_t)nrhs));
     LCHK(grow(P.d_csY, (size_t)yr * (size_t)nrhs));
-    LCHK(upload_cols(P, P.d_csX, X, ldx, xr, nrhs));
+    LCHK(upload_cols(P.d_csX, X, ldx, xr, nrhs, P.stream));
     LCHK(spmv_dev(P, trans, P.d_csX.p, xr, nullptr, 0, P.d_csY.p, yr, nrhs));
     return download_cols(P, P.d_csY, Y, ldy, yr, nrhs);
 }
@@ -582,47 +611,35 @@ int stmmqr_plan_spmv(stmmqr_plan *plan, int trans, const double *X, stm_long ldx
 int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int refine,
                                  int on_device, double *info)
 {
-    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    PASS(check_factored(plan));
     stmmqr_plan &P = *plan;
     const long m = P.m, n = P.n;
     if (!B || !X || nrhs < 0 || refine < 0 || ldb < m || ldx < n) return fail(STMMQR_ERR_INVALID, "bad seminormal solve arguments");
     if (!P.pattern_set) return fail(STMMQR_ERR_INVALID, "pattern of A was never given");
-    HIPCHK(hipSetDevice(P.device));
-    LCHK(ensure_rowmap(P));                          // (fills level_lds_rt on the first resident-factor call of the plan)
-    for (int need : P.level_lds_rt)                  // (the R' \ step: before any launch of the solve)
-        if (need > 131072) return fail(STMMQR_ERR_TOO_LARGE, "a front is too wide for the one-workgroup R' solve");
+    PASS(begin_resident_op(P));
+    PASS(ensure_rt(P));                              // (the R' \ step: refused before any launch of the solve)
     LCHK(stm_ensure_a_index(P));
     if (info) *info = 0;
     if (nrhs == 0) return 0;
     hipStream_t st = P.stream;
-    if (!P.d_U.p) {
-        LCHK(P.d_U.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, P.rjsize)));
-        LCHK(P.d_Xr.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, m)));
-    }
-    const int nbmax = rhs_batch_max();
-    const size_t mm = (size_t)std::max(1L, m), nn = (size_t)std::max(1L, n), nbm = (size_t)std::min<stm_long>(nbmax, nrhs);
-    LCHK(grow(P.d_csB, mm * (size_t)nrhs));
-    LCHK(grow(P.d_csX, nn * (size_t)nrhs));
+    const size_t mm = (size_t)std::max(1L, m), nn = (size_t)std::max(1L, n), nbm = (size_t)std::min<stm_long>(rhs_batch_max(), nrhs);
+    LCHK(grow(P.d_csB, mm * (size_t)nrhs)); LCHK(grow(P.d_csX, nn * (size_t)nrhs));
     LCHK(grow(P.d_csR, mm * nbm)); LCHK(grow(P.d_csY, mm * nbm));
     LCHK(grow(P.d_csZ, nn * nbm)); LCHK(grow(P.d_csD, nn * nbm));
     LCHK(grow(P.d_csN, 3 * (size_t)nrhs + 1));
-    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
-    if (on_device) {
-        for (stm_long j = 0; j < nrhs; j++)
-            HIPCHK(hipMemcpyAsync(P.d_csB.p + j * m, B + j * ldb, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
-    } else LCHK(upload_cols(P, P.d_csB, B, ldb, m, nrhs));
-    for (stm_long j = 0; j < nrhs; j += nbmax) {
-        const int nb = (int)std::min<stm_long>(nbmax, nrhs - j);
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), P.stream));
+    PASS(copy_cols(P.d_csB.p, m, B, ldb, m, nrhs, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    PASS(for_each_batch(P, nrhs, [&](stm_long j, int nb) -> int {
         const double *b = P.d_csB.p + j * m;
         double *x = P.d_csX.p + j * n;
         LCHK(spmv_dev(P, 1, b, m, nullptr, 0, P.d_csZ.p, n, nb));                        // z = A'b
-        LCHK(rt_vectors(P, P.d_csZ.p, P.d_csY.p, nb));                                    // y = R' \ (E'z)
-        LCHK(r_vectors(P, P.d_csY.p, x, nb));                                             // x = E (R \ y)
+        LCHK(rt_vectors(P, P.d_csZ.p, P.d_csY.p, nb, true));                              // y = R' \ (E'z)
+        LCHK(r_vectors(P, P.d_csY.p, x, nb, true));                                       // x = E (R \ y)
         for (int it = 0; it < refine; it++) {
             LCHK(spmv_dev(P, 0, x, n, b, m, P.d_csR.p, m, nb));                          // r = b - A x
             LCHK(spmv_dev(P, 1, P.d_csR.p, m, nullptr, 0, P.d_csZ.p, n, nb));             // A'r
-            LCHK(rt_vectors(P, P.d_csZ.p, P.d_csY.p, nb));
-            LCHK(r_vectors(P, P.d_csY.p, P.d_csD.p, nb));
+            LCHK(rt_vectors(P, P.d_csZ.p, P.d_csY.p, nb, true));
+            LCHK(r_vectors(P, P.d_csY.p, P.d_csD.p, nb, true));
             LCHK(stm_launch_add_cols((int)n, nb, P.d_csD.p, n, x, n, st));                // x += E R^-1 R^-T E' A'r
         }
         if (info) {
@@ -632,58 +649,37 @@ int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ld
             LCHK(stm_launch_colnorm2(n, x, n, nb, P.d_csN.p + nrhs + j, st));
             LCHK(stm_launch_colnorm2(m, b, m, nb, P.d_csN.p + 2 * nrhs + j, st));
         }
-    }
+        return 0;
+    }));
     if (info) {
         LCHK(stm_launch_colnorm2(P.anz, P.d_Ax.p, std::max(1L, P.anz), 1, P.d_csN.p + 3 * nrhs, st));   // |A|_F^2
         std::vector<double> nr((size_t)(3 * nrhs + 1));
         HIPCHK(hipMemcpyAsync(nr.data(), P.d_csN.p, nr.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        const double af = std::sqrt(nr[(size_t)(3 * nrhs)]);
-        double worst = 0;
-        for (stm_long j = 0; j < nrhs; j++) {
-            const double den = af * (af * std::sqrt(nr[(size_t)(nrhs + j)]) + std::sqrt(nr[(size_t)(2 * nrhs + j)]));
-            const double q = std::sqrt(nr[(size_t)j]);
-            const double v = den > 0 ? q / den : (q > 0 ? INFINITY : 0.0);
-            worst = std::max(worst, v);
-        }
-        *info = worst;
+        *info = stm_seminormal_info(std::sqrt(nr[(size_t)(3 * nrhs)]), nr.data(), nr.data() + nrhs, nr.data() + 2 * nrhs, nrhs);
     }
-    if (on_device) {
-        for (stm_long j = 0; j < nrhs; j++)
-            HIPCHK(hipMemcpyAsync(X + j * ldx, P.d_csX.p + j * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-    } else LCHK(download_cols(P, P.d_csX, X, ldx, n, nrhs));
-    return check_device_err(P, "internal: live pivot count of a front differs from its rank");
+    LCHK(download_cols(P, P.d_csX, X, ldx, n, nrhs, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return end_resident_op(P);
 }
 
 // Least squares with the right-hand sides carried through the factorization; see include/stmmqr_hip.h.  The plan holds the R of
-// [A B] (n = P.n - nrhs columns of A, ntol = n).  The back substitution is rsolve_vector's pass over the tree on a view of the
-// factorization that ends at column n (stmmqr_carried.hip): fronts that hold B columns as pivots have fp cut back to their A pivots
+// [A B] (n = P.n - nrhs columns of A, ntol = n).  The back substitution is r_pass on a view of the factorization that ends at
+// column n (stmmqr_carried.hip): fronts that hold B columns as pivots have fp cut back to their A pivots
 // and their live A pivots as rank, y = 0 and x(n + j) = -1 for right-hand side j -- so y - R12 x is C(:, j) minus the A part, and
 // no diagonal entry of the B block is ever a divisor.
 int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_long ldx, double *resid, int on_device)
 {
-    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    PASS(check_factored(plan));
     stmmqr_plan &P = *plan;
     if (nrhs < 1 || nrhs > P.n) return fail(STMMQR_ERR_INVALID, "carried solve: nrhs must be between 1 and the number of columns of the factorized [A B]");
     const long m = P.m, na = P.n, n = P.n - nrhs;
     if (!X || ldx < n) return fail(STMMQR_ERR_INVALID, "bad carried solve arguments");
-    if (P.last_ntol != n)
-        return fail(STMMQR_ERR_INVALID, "carried solve: the factorization was made with ntol = " + std::to_string(P.last_ntol) + ", not n = " +
-                                            std::to_string(n) + " (the columns of B must not be rank-tested, those of A must)");
-    if (P.has_qfill)
-        for (long j = n; j < na; j++)
-            if (P.Qfill[(size_t)j] != j)
-                return fail(STMMQR_ERR_INVALID, "carried solve: column " + std::to_string(j) + " of [A B] is permuted (Qfill must be the identity on the B columns)");
-    HIPCHK(hipSetDevice(P.device));
-    LCHK(ensure_rowmap(P));
+    PASS(check_carried_view(P, n));
+    PASS(begin_resident_op(P));
     hipStream_t st = P.stream;
     const auto &LV = P.glevels[0];
     // ---- the view: FrontSym of the array the resident-factor kernels read (res_ctx) with fp cut back, the B fronts level by level ----
-    std::vector<FrontSym> vs = P.recycle ? P.fs_scr : P.fs;
-    if (P.recycle)
-        for (long f = 0; f < P.nf; f++)
-            if (P.kept[(size_t)f]) vs[(size_t)f].foff = (long long)((P.d_F.p + P.fs[f].foff) - P.d_scr.p);     // (as ensure_scratch)
+    std::vector<FrontSym> vs = resident_front_syms(P);
     std::vector<int> blist, boff(LV.size() + 1, 0);
     for (size_t l = 0; l < LV.size(); l++) {
         for (int q = 0; q < LV[l].n_all; q++) {
@@ -703,43 +699,32 @@ int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_l
     if (P.nf > 0) HIPCHK(hipMemcpyAsync(P.d_fnum_car.p, P.d_fnum.p, (size_t)P.nf * sizeof(FrontNum), hipMemcpyDeviceToDevice, st));
     LCHK(grow(P.d_carN, (size_t)nrhs));
     HIPCHK(hipMemsetAsync(P.d_carN.p, 0, (size_t)nrhs * sizeof(double), st));
-    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
-    if ((size_t)(std::max(1L, n) * nrhs) > P.d_Yall.n) LCHK(P.d_Yall.alloc((size_t)(std::max(1L, n) * nrhs)));
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), P.stream));
+    LCHK(grow(P.d_Yall, (size_t)(std::max(1L, n) * nrhs)));
     const DevCtx ct = res_ctx(P);
     DevCtx cv = ct;
     cv.fs = P.d_fs_car.p; cv.fnum = P.d_fnum_car.p;
-    const int *L0 = P.d_lists.p;
-    const int nbmax = rhs_batch_max();
-    for (stm_long j0 = 0; j0 < nrhs; j0 += nbmax) {
-        const int nb = (int)std::min<stm_long>(nbmax, nrhs - j0);
-        LCHK(ensure_rhs_batch(P, nb));
-        const RhsBatch B = rhs_strides(P);
+    PASS(for_each_batch(P, nrhs, [&](stm_long j0, int nb) -> int {
         HIPCHK(hipMemsetAsync(P.d_W.p, 0, (size_t)nb * (size_t)std::max(1L, m) * sizeof(double), st));
         HIPCHK(hipMemsetAsync(P.d_Xs.p, 0, (size_t)nb * (size_t)na * sizeof(double), st));
-        LCHK(stm_launch_carried_seed(P.d_Xs.p, B.x, (int)n, (int)j0, nb, st));
-        for (size_t l = LV.size(); l-- > 0;) {
-            LCHK(level_to_front_form(P, l));
-            // (the first pass sets the view's ranks of the level's B fronts before its kernels read them, and takes the residual norms
-            //  while the level is in front form)
-            if (j0 == 0) LCHK(stm_launch_carried_view(ct, P.d_carlist.p + boff[l], boff[l + 1] - boff[l], (int)n, P.d_fnum_car.p, P.d_carN.p, st));
-            LCHK(stm_launch_rsolve(cv, L0 + LV[l].all_off, LV[l].n_all, P.d_Rj.p, P.d_W.p, P.d_Xs.p, P.level_lds_rs[l], P.d_err.p, st, nb, B));
-            const auto &Q = P.level_qbig[l];
-            LCHK(stm_launch_rsolve_big(cv, P.d_qb.p + Q.off, Q.n, Q.live_rsteps, Q.max_nslab, P.d_Rj.p, P.d_W.p, P.d_Xs.p, P.d_Xf.p,
-                                       P.d_Dq.p, P.d_Rm.p + Q.off, P.d_err.p, st, nb, B));
-        }
+        LCHK(stm_launch_carried_seed(P.d_Xs.p, na, (int)n, (int)j0, nb, st));
+        // (the first pass sets the view's ranks of the level's B fronts before its kernels read them, and takes the residual norms
+        //  while the level is in front form)
+        PASS(r_pass(P, cv, nb, [&](size_t l) {
+            return j0 == 0 ? stm_launch_carried_view(ct, P.d_carlist.p + boff[l], boff[l + 1] - boff[l], (int)n, P.d_fnum_car.p, P.d_carN.p, st) : 0;
+        }));
         LCHK(stm_launch_perm(P.d_Xs.p, P.has_qfill ? P.d_Qfill.p : nullptr, P.d_Yall.p + j0 * n, (int)n, 1, st, nb, na, n));   // X[Qfill[j]] = x[j], j < n
-    }
+        return 0;
+    }));
     if (on_device) {
-        if (n > 0)
-            HIPCHK(hipMemcpy2DAsync(X, (size_t)ldx * sizeof(double), P.d_Yall.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
-                                    (size_t)nrhs, hipMemcpyDeviceToDevice, st));
+        PASS(copy_cols(X, ldx, P.d_Yall.p, n, n, nrhs, hipMemcpyDeviceToDevice, st));
         if (resid) HIPCHK(hipMemcpyAsync(resid, P.d_carN.p, (size_t)nrhs * sizeof(double), hipMemcpyDeviceToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
     } else {
         if (resid) HIPCHK(hipMemcpyAsync(resid, P.d_carN.p, (size_t)nrhs * sizeof(double), hipMemcpyDeviceToHost, st));
         LCHK(download_cols(P, P.d_Yall, X, ldx, n, nrhs));
     }
-    return check_device_err(P, "internal: live pivot count of a front differs from its rank");
+    return end_resident_op(P);
 }
 
 // diag(((A E)_live' (A E)_live)^-1) by selected inversion of R'R; see include/stmmqr_hip.h and stmmqr_selinv.hip.  The frontal tree is
@@ -750,27 +735,18 @@ int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_l
 // columns of A as well -- the B columns are the last entries of every front's list.
 int stmmqr_plan_covariance_diag(stmmqr_plan *plan, stm_long ncol, double *var, int on_device)
 {
-    if (!plan || !plan->factored) return fail(STMMQR_ERR_INVALID, "no factorization held by the plan");
+    PASS(check_factored(plan));
     stmmqr_plan &P = *plan;
     const long n = P.n;
     if (!var) return fail(STMMQR_ERR_INVALID, "covariance: var is NULL");
     if (ncol < 0 || ncol > n)
         return fail(STMMQR_ERR_INVALID, "covariance: ncol = " + std::to_string(ncol) + " is not between 0 and the " + std::to_string(n) + " columns of the plan");
-    if (ncol < n) {                                          // (the conditions and messages of stmmqr_plan_solve_carried)
-        if (P.last_ntol != ncol)
-            return fail(STMMQR_ERR_INVALID, "carried solve: the factorization was made with ntol = " + std::to_string(P.last_ntol) + ", not n = " +
-                                                std::to_string(ncol) + " (the columns of B must not be rank-tested, those of A must)");
-        if (P.has_qfill)
-            for (long j = ncol; j < n; j++)
-                if (P.Qfill[(size_t)j] != j)
-                    return fail(STMMQR_ERR_INVALID, "carried solve: column " + std::to_string(j) + " of [A B] is permuted (Qfill must be the identity on the B columns)");
-    }
+    if (ncol < n) PASS(check_carried_view(P, ncol));
     bool whole = P.glevels.size() == 1;
     for (long f = 0; f < P.nf && whole; f++) whole = P.group[(size_t)f] == 0 && !((size_t)f < P.shared.size() && P.shared[(size_t)f]);
     if (!whole)
         return fail(STMMQR_ERR_INVALID, "covariance: the plan does not hold the whole tree in one group (groups were set, or fronts are imported or shared)");
-    HIPCHK(hipSetDevice(P.device));
-    LCHK(ensure_rowmap(P));
+    PASS(begin_resident_op(P));
     if (ncol == 0) return 0;
     hipStream_t st = P.stream;
     const auto &LV = P.glevels[0];
@@ -812,7 +788,7 @@ int stmmqr_plan_covariance_diag(stmmqr_plan *plan, stm_long ncol, double *var, i
     double *dv = on_device ? var : dVar.p;
     HIPCHK(hipMemcpyAsync(dSd.p, sd.data(), sd.size() * sizeof(SiDesc), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(dv, 0, (size_t)ncol * sizeof(double), st));                       // (dead columns: 0)
-    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), P.stream));
     const DevCtx c = res_ctx(P);
     LCHK(stm_launch_si_prep(c, (int)nf, dSd.p, dLc.p, dPos.p, dRm.p, P.d_err.p, st));
     for (size_t l = LV.size(); l-- > 0;) {
@@ -821,7 +797,7 @@ int stmmqr_plan_covariance_diag(stmmqr_plan *plan, stm_long ncol, double *var, i
                                  P.has_qfill ? P.d_Qfill.p : nullptr, dWk.p, dZ.p, dv, st));
     }
     if (!on_device) HIPCHK(hipMemcpyAsync(var, dv, (size_t)ncol * sizeof(double), hipMemcpyDeviceToHost, st));
-    return check_device_err(P, "internal: live pivot count of a front differs from its rank");      // (synchronizes: sd and the buffers are done with)
+    return end_resident_op(P);                               // (synchronizes: sd and the buffers are done with)
 }
 
 int stmmqr_plan_keep_h(const stmmqr_plan *plan) { return plan ? plan->keep_h : -1; }
@@ -831,7 +807,7 @@ struct stm_aop {
     int device = 0;
     hipStream_t st = nullptr;
     long m = 0, n = 0;
-    DevBuf<int> cp, ci, rp, rj, rq;
+    AIndexDev A;
     DevBuf<double> ax, X, B, Y;
     ~stm_aop() { if (st) (void)hipStreamDestroy(st); }
 };
@@ -848,21 +824,19 @@ int stm_aop_create(int device, stm_long m, stm_long n, const stm_long *Ap, const
     (void)hipGetDevice(&op->device);
     HIPCHK(hipStreamCreateWithFlags(&op->st, hipStreamNonBlocking));
     op->m = m; op->n = n;
-    std::vector<int> acp((size_t)n + 1), aci((size_t)std::max(1L, anz)), arp((size_t)m + 1, 0), arj((size_t)std::max(1L, anz)),
-        arq((size_t)std::max(1L, anz));
+    std::vector<int> acp((size_t)n + 1), aci((size_t)std::max(1L, anz)), acol((size_t)std::max(1L, anz)), arp, arj, arq;
     for (long j = 0; j <= n; j++) acp[(size_t)j] = (int)Ap[j];
     for (long p = 0; p < anz; p++) {
         if (Ai[p] < 0 || Ai[p] >= m) return fail(STMMQR_ERR_INVALID, "row index out of range");
-        aci[(size_t)p] = (int)Ai[p]; arp[(size_t)Ai[p] + 1]++;
+        aci[(size_t)p] = (int)Ai[p];
     }
-    for (long i = 0; i < m; i++) arp[(size_t)i + 1] += arp[(size_t)i];
-    std::vector<int> next(arp.begin(), arp.end() - 1);
     for (long j = 0; j < n; j++)
-        for (long p = Ap[j]; p < Ap[j + 1]; p++) { const int q = next[(size_t)Ai[p]]++; arj[(size_t)q] = (int)j; arq[(size_t)q] = (int)p; }
+        for (long p = Ap[j]; p < Ap[j + 1]; p++) acol[(size_t)p] = (int)j;
+    stm_row_form(m, anz, aci.data(), acol.data(), arp, arj, arq);
     std::vector<double> ax(Ax, Ax + anz);
     if (ax.empty()) ax.push_back(0.0);
-    LCHK(op->cp.upload(acp, op->st)); LCHK(op->ci.upload(aci, op->st)); LCHK(op->rp.upload(arp, op->st));
-    LCHK(op->rj.upload(arj, op->st)); LCHK(op->rq.upload(arq, op->st)); LCHK(op->ax.upload(ax, op->st));
+    LCHK(op->A.cp.upload(acp, op->st)); LCHK(op->A.ci.upload(aci, op->st)); LCHK(op->A.rp.upload(arp, op->st));
+    LCHK(op->A.rj.upload(arj, op->st)); LCHK(op->A.rq.upload(arq, op->st)); LCHK(op->ax.upload(ax, op->st));
     HIPCHK(hipStreamSynchronize(op->st));
     *out = op.release();
     return 0;
@@ -875,20 +849,11 @@ int stm_aop_apply(stm_aop *op, int trans, const double *X, stm_long ldx, const d
     const long xr = trans ? op->m : op->n, yr = trans ? op->n : op->m;
     if (nrhs <= 0 || yr == 0) return 0;
     HIPCHK(hipSetDevice(op->device));
-    auto up = [&](DevBuf<double> &d, const double *H, long ld, long rows) -> int {
-        if (d.n < (size_t)(rows * nrhs) || !d.p) LCHK(d.alloc((size_t)std::max(1L, rows * nrhs)));
-        if (rows > 0)
-            HIPCHK(hipMemcpy2DAsync(d.p, (size_t)rows * sizeof(double), H, (size_t)ld * sizeof(double), (size_t)rows * sizeof(double),
-                                    (size_t)nrhs, hipMemcpyHostToDevice, op->st));
-        return 0;
-    };
-    LCHK(up(op->X, X, ldx, xr));
-    if (B) LCHK(up(op->B, B, ldb, yr));
-    if (op->Y.n < (size_t)(yr * nrhs) || !op->Y.p) LCHK(op->Y.alloc((size_t)(yr * nrhs)));
-    if (trans) LCHK(stm_launch_spmv((int)op->n, op->cp.p, op->ci.p, nullptr, op->ax.p, op->X.p, xr, nullptr, 0, op->Y.p, yr, nrhs, op->st));
-    else LCHK(stm_launch_spmv((int)op->m, op->rp.p, op->rj.p, op->rq.p, op->ax.p, op->X.p, xr, B ? op->B.p : nullptr, yr, op->Y.p, yr, nrhs, op->st));
-    HIPCHK(hipMemcpy2DAsync(Y, (size_t)ldy * sizeof(double), op->Y.p, (size_t)yr * sizeof(double), (size_t)yr * sizeof(double), (size_t)nrhs,
-                            hipMemcpyDeviceToHost, op->st));
+    LCHK(upload_cols(op->X, X, ldx, xr, nrhs, op->st));
+    if (B) LCHK(upload_cols(op->B, B, ldb, yr, nrhs, op->st));
+    LCHK(grow(op->Y, (size_t)(yr * nrhs)));
+    LCHK(spmv(op->A, op->ax.p, op->m, op->n, trans, op->X.p, xr, (B && !trans) ? op->B.p : nullptr, trans ? 0 : yr, op->Y.p, yr, nrhs, op->st));
+    PASS(copy_cols(Y, ldy, op->Y.p, yr, yr, nrhs, hipMemcpyDeviceToHost, op->st));
     HIPCHK(hipStreamSynchronize(op->st));
     return 0;
 }
@@ -896,7 +861,7 @@ int stm_aop_apply(stm_aop *op, int trans, const double *X, stm_long ldx, const d
 // Least squares by the corrected seminormal equations on a SparseQR object (with or without H): x = E R^-1 R^-T E' A'b, then
 // `refine` times r = b - A x, x += E R^-1 R^-T E' A'r.  A' and A are the caller's full matrix (singleton rows and columns
 // included) on the device (stm_aop); R'\ and R\ are systems 3 and 1 of stmmqr_sparseqr_solve (singleton rows + the plan).
-// info: max over the columns of |A'r| / (|A|_F (|A|_F |x| + |b|)).
+// info: stm_seminormal_info of host sums.
 int stmmqr_sparseqr_solve_seminormal(stmmqr_qr *qr, const stm_long *Ap, const stm_long *Ai, const double *Ax, const double *B, stm_long ldb,
                                      stm_long nrhs, double *X, stm_long ldx, int refine, double *info)
 {
@@ -935,16 +900,12 @@ int stmmqr_sparseqr_solve_seminormal(stmmqr_qr *qr, const stm_long *Ap, const st
             if (!e) {
                 double af = 0;
                 for (stm_long p = 0; p < Ap[n]; p++) af += Ax[p] * Ax[p];
-                af = std::sqrt(af);
-                double worst = 0;
+                std::vector<double> zz(K, 0.0), xx(K, 0.0), bb(K, 0.0);
                 for (stm_long j = 0; j < nrhs; j++) {
-                    double zz = 0, xx = 0, bb = 0;
-                    for (stm_long k = 0; k < n; k++) { zz += z[(size_t)k + (size_t)j * N] * z[(size_t)k + (size_t)j * N]; xx += X[k + j * ldx] * X[k + j * ldx]; }
-                    for (stm_long i = 0; i < m; i++) bb += B[i + j * ldb] * B[i + j * ldb];
-                    const double den = af * (af * std::sqrt(xx) + std::sqrt(bb)), q = std::sqrt(zz);
-                    worst = std::max(worst, den > 0 ? q / den : (q > 0 ? INFINITY : 0.0));
+                    for (stm_long k = 0; k < n; k++) { zz[j] += z[(size_t)k + (size_t)j * N] * z[(size_t)k + (size_t)j * N]; xx[j] += X[k + j * ldx] * X[k + j * ldx]; }
+                    for (stm_long i = 0; i < m; i++) bb[j] += B[i + j * ldb] * B[i + j * ldb];
                 }
-                *info = worst;
+                *info = stm_seminormal_info(std::sqrt(af), zz.data(), xx.data(), bb.data(), nrhs);
             }
         }
     } catch (const std::bad_alloc &) {
@@ -953,5 +914,3 @@ int stmmqr_sparseqr_solve_seminormal(stmmqr_qr *qr, const stm_long *Ap, const st
     stm_aop_destroy(op);
     return e;
 }
-
-}  // extern "C"

@@ -4,11 +4,13 @@
 // For every Matrix-Market file on the command line: the reader (stmmqr_read_matrix_market: hostile files included), the symbolic
 // analysis in natural order (stmmqr_analyze) and the host half of SparseQR() (singletons, COLAMD, analysis:
 // stmmqr_sparseqr_symbolic).  The device entry points stmmqr_sparseqr.cpp refers to are never called here; they are stubbed below.
+// Before the files: the index arithmetic of the products with A (stm_row_form) and the seminormal solves' info (stmmqr_internal.h).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 #include "../include/stmmqr_hip.h"
+#include "../stm-multifrontal-qr-factorization-empowered-by-gcn_amd/csrc/stmmqr_internal.h"
 
 extern "C" int stm_fail(int code, const char *msg) { fprintf(stderr, "[sanitize_host] library error %d: %s\n", code, msg ? msg : ""); return code; }
 // device half: not part of this build
@@ -21,8 +23,24 @@ int stmmqr_plan_qmult(stmmqr_plan *, int, double *, stm_long, stm_long) { return
 int stmmqr_plan_rsolve(stmmqr_plan *, int, const double *, stm_long, double *, stm_long, stm_long) { return STMMQR_ERR_DEVICE; }
 }
 
+// a 5 x 4 matrix with an empty row (3) and an empty column (2), columns {0, 4}, {1, 0, 2}, {}, {4, 1}: the row form keeps storage order
+static bool helpers_ok()
+{
+    const int row[7] = {0, 4, 1, 0, 2, 4, 1}, col[7] = {0, 0, 1, 1, 1, 3, 3};
+    const std::vector<int> erp = {0, 2, 4, 5, 5, 7}, erj = {0, 1, 1, 3, 1, 0, 3}, erq = {0, 3, 2, 6, 4, 1, 5};
+    std::vector<int> rp, rj, rq;
+    stm_row_form(5, 7, row, col, rp, rj, rq);
+    bool ok = rp == erp && rj == erj && rq == erq;
+    stm_row_form(3, 0, row, col, rp, rj, rq);                        // no entries: the arrays still have an element to upload
+    ok = ok && rp == std::vector<int>(4, 0) && rj.size() == 1 && rq.size() == 1;
+    const double zz[3] = {4.0, 0.0, 1.0}, xx[3] = {1.0, 0.0, 0.0}, bb[3] = {9.0, 0.0, 0.0};
+    ok = ok && stm_seminormal_info(2.0, zz, xx, bb, 2) == 0.2 && std::isinf(stm_seminormal_info(2.0, zz, xx, bb, 3));   // 0 / 0: 0, q / 0: inf
+    return ok && stm_seminormal_info(0.0, zz, xx, bb, 0) == 0.0;
+}
+
 int main(int argc, char **argv)
 {
+    if (!helpers_ok()) { fprintf(stderr, "[sanitize_host] stm_row_form / stm_seminormal_info: wrong result\n"); return 1; }
     int nread = 0, nrefused = 0, nanalyzed = 0;
     for (int a = 1; a < argc; a++) {
         stm_long m = 0, n = 0, nnz = 0, *Ap = nullptr, *Ai = nullptr;

@@ -328,6 +328,40 @@ def test_seminormal_rank_deficient(pkg, name):
         p.close()
 
 
+def seminormal_by_parts(p, B):
+    """x = E R^-1 R^-T E' A'b spelled out with the plan's own operations: the launches of solve_seminormal(refine=0), batch by batch"""
+    return p.rsolve(1, p.rsolve(3, p.spmv(B, 1)))
+
+
+def check_seminormal_parts(pkg, name, keep_h, nrhs):
+    g = load_golden(name)
+    S, p = plan_for(pkg, g, keep_h)
+    try:
+        if name == "syn_rankdef_grid":
+            assert p.download().rank < S.n                 # (dead columns; its Qfill is no identity)
+        B = np.random.default_rng(17).standard_normal((S.m, nrhs))
+        X, _ = p.solve_seminormal(B, refine=0)
+        Xp = seminormal_by_parts(p, B)
+        assert np.array_equal(X.view(np.uint64), Xp.view(np.uint64))
+    finally:
+        p.close()
+
+
+@pytest.mark.parametrize("name", ["syn_grid2d", "syn_rankdef_grid"])
+@pytest.mark.parametrize("keep_h", [False, True])
+@pytest.mark.parametrize("nrhs", [3, 33])
+def test_seminormal_equals_its_parts(pkg, name, keep_h, nrhs):
+    """the fused solve runs the passes that rsolve and spmv run one by one: the same bits, with a full batch of 32 plus one as well"""
+    check_seminormal_parts(pkg, name, keep_h, nrhs)
+
+
+@pytest.mark.parametrize("keep_h", [False, True])
+def test_seminormal_equals_its_parts_level_rebuild(pkg, env, keep_h):
+    """... with recycled slabs and no cache of the front forms: every pass puts every level back into front form"""
+    env(STMMQR_RECYCLE="2", STMMQR_RESIDENT_CACHE="0")
+    check_seminormal_parts(pkg, "syn_rankdef_grid", keep_h, 33)
+
+
 def test_seminormal_too_wide_front(pkg):
     """c5mini_standin has a front too wide for the one-workgroup R' solve: on a FRESH plan (nothing resident-factor related has run
     yet) the seminormal solve returns the error of rsolve system 3, before any launch of the solve"""

@@ -245,6 +245,22 @@ def test_all_qmult_methods_and_solve_systems(pkg, oracle, name):
         plan.close()
 
 
+@pytest.mark.parametrize("name", ["syn_grid2d", "syn_rankdef_grid"])
+@pytest.mark.parametrize("nrhs", [3, 33])
+def test_solve_equals_its_parts(pkg, name, nrhs):
+    """solve is QR_qmult(QR_QTX) followed by QR_solve(QR_RETX_EQUALS_B) without the trip to the host in between: the same passes over
+    the tree, so the same bits (33: a full batch of 32 plus one)"""
+    g = load_golden(name)
+    S, plan = factorized_plan(pkg, g)
+    try:
+        B = np.random.default_rng(29).standard_normal((S.m, nrhs))
+        X = plan.solve(B)
+        Xp = plan.rsolve(1, plan.qmult(0, B))
+        assert np.array_equal(X.view(np.uint64), Xp.view(np.uint64))
+    finally:
+        plan.close()
+
+
 @pytest.mark.parametrize("name", ["grid20_standin", "lns_3937", "bcsstk14", "syn_rankdef_grid", "epb1"])
 def test_batched_right_hand_sides(pkg, oracle, monkeypatch, name):
     """QR_qmult / QR_solve take BLOCKS of right-hand sides (qr_panel, SparseQR.c:1591-1706).  Here every launch of a pass over the tree
