@@ -424,9 +424,40 @@ int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_l
  * u cond(A)^2 times the largest one -- as the normal equations would.  Up to cond(A) ~ 1e7 every variance has digits to spare
  * (measured: DESIGN.md 6h); on lns_3937 (cond ~ 1e11) 45 of 1822 variances are off by more than 1e-3 relative and four are negative.
  * There |stmmqr_plan_rsolve(system 3, e_j)|^2 gives column j to u cond(A), one column at a time.
- * Out of scope: off-diagonal entries of the inverse as an output, and a stmmqr_sparseqr_* entry (the singleton block R1 lives on the
- * host and is no part of the plan; the stmmqr_ls object removes no singletons and is the home of this feature). */
+ * Entries off the diagonal and the leverages of the rows come from the same blocks: stmmqr_plan_covariance_entries and
+ * stmmqr_plan_leverage below.  Out of scope: entries outside the pattern of the selected inverse, and a stmmqr_sparseqr_* entry (the
+ * singleton block R1 lives on the host and is no part of the plan; the stmmqr_ls object removes no singletons and is the home of
+ * this feature). */
 int stmmqr_plan_covariance_diag(stmmqr_plan *plan, stm_long ncol, double *var, int on_device);
+
+/* Leverages of a least-squares fit.  With Z = ((A E)_live' (A E)_live)^-1 as above and a_i = row i of the factorized matrix
+ * restricted to its first ncol columns (the values of the last factorization), lev[i] = a_i' Z a_i for i < m in the caller's row
+ * order: the diagonal of the orthogonal projector onto the span of the live columns (the hat matrix), 0 <= lev[i] <= 1 and
+ * sum_i lev[i] = the number of live columns.  Dead columns take no part; an empty row gives 0.
+ * The selected inversion of stmmqr_plan_covariance_diag is run once and its blocks are read while they are resident: a row of A makes
+ * its columns a clique of A'A, so every Z(j, k) the row needs lies in the block of the front where the earlier of the two columns is
+ * pivotal.  No solve with R' is made and there is no limit on the width of a front.  A row costs nnz(row)^2 lookups on one
+ * wavefront: a matrix with a dense row of tens of thousands of entries is slow here.
+ *   var non-NULL [ncol]: receives exactly what stmmqr_plan_covariance_diag(plan, ncol, var, on_device) writes (the same bits), from the
+ *   same inversion.  on_device: lev and var are device pointers.
+ * Needs the pattern of A (stmmqr_factorize_device was given Ap / Ai once): otherwise STMMQR_ERR_INVALID, "pattern of A was never
+ * given".  lev NULL: STMMQR_ERR_INVALID.  Every other refusal, the messages and the memory behaviour are those of
+ * stmmqr_plan_covariance_diag; the call's own tables (S's row pointers and column indices, one int per column) are released before it
+ * returns as well.  Accuracy: as the variances, an error of about u cond(A)^2 (measured: DESIGN.md 6i).
+ * The same bits from two calls, from plans with and without H, and for host and device output. */
+int stmmqr_plan_leverage(stmmqr_plan *plan, stm_long ncol, double *lev /* [m] */, double *var /* [ncol] or NULL */, int on_device);
+
+/* Entries of the inverse: out[p] = Z(I[p], J[p]), p < npairs, with Z as above and the column indices in the caller's column order
+ * (0 <= I[p], J[p] < ncol).  I and J are host arrays; on_device: out is a device pointer.
+ * A pair is in the pattern of the selected inverse when its columns are equal, or when the later one in R's column order is a column
+ * of the front whose pivots hold the earlier one (two columns that share a row of A always are).  This is decided on the host from the
+ * symbolic analysis before anything is allocated or launched: the first pair outside the pattern gives STMMQR_ERR_INVALID with a
+ * message that names p and the two columns, out is not written and the plan stays usable.
+ * An in-pattern pair with a dead column gives exactly 0; (i, j) and (j, i) give the same bits; (j, j) gives the bits of var[j].
+ * npairs < 0, or npairs > 0 with out, I or J NULL: STMMQR_ERR_INVALID.  Every other refusal, the messages and the memory behaviour
+ * are those of stmmqr_plan_covariance_diag.  The correlation of x_i and x_j is Z(i, j) / sqrt(Z(i, i) Z(j, j)). */
+int stmmqr_plan_covariance_entries(stmmqr_plan *plan, stm_long ncol, stm_long npairs, const stm_long *I, const stm_long *J,
+                                   double *out /* [npairs] */, int on_device);
 
 /* dense single-front kernels on host buffers (inner seams without the cc argument) */
 stm_long stmmqr_front(stm_long m, stm_long n, stm_long npiv, double tol, stm_long ntol, double *F,
@@ -621,6 +652,10 @@ stmmqr_plan *stmmqr_ls_plan(stmmqr_ls *ls);
 int stmmqr_ls_info(const stmmqr_ls *ls, double *info);
 int stmmqr_ls_resid(const stmmqr_ls *ls, double *resid);   /* [nrhs] host array: the residual norms of the last solve */
 int stmmqr_ls_covariance_diag(stmmqr_ls *ls, double *var, int on_device);   /* after a solve: stmmqr_plan_covariance_diag with ncol = n of A */
+/* after a solve: stmmqr_plan_leverage / stmmqr_plan_covariance_entries with ncol = n of A (lev [m], var [n] or NULL; column indices of A).
+ * They refuse as stmmqr_ls_covariance_diag does: null object, the host half only, no solve yet. */
+int stmmqr_ls_leverage(stmmqr_ls *ls, double *lev, double *var, int on_device);
+int stmmqr_ls_covariance_entries(stmmqr_ls *ls, stm_long npairs, const stm_long *I, const stm_long *J, double *out, int on_device);
 void stmmqr_ls_free(stmmqr_ls *ls);
 
 void stmmqr_shutdown(void);                           /* optional end-of-use call for dlopen()ing hosts: device sync  */

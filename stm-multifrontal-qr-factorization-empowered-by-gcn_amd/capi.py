@@ -152,6 +152,8 @@ lib.stmmqr_plan_solve_seminormal.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C
                                              c_double_p]
 lib.stmmqr_plan_solve_carried.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
 lib.stmmqr_plan_covariance_diag.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_int]
+lib.stmmqr_plan_leverage.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int]
+lib.stmmqr_plan_covariance_entries.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_set_keep_h.argtypes = [C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_solve_seminormal.argtypes = [C.c_void_p, c_long_p, c_long_p, c_double_p, c_double_p, C.c_long, C.c_long, c_double_p,
                                                  C.c_long, C.c_int, c_double_p]
@@ -599,6 +601,37 @@ class HipQR:
         _check(lib.stmmqr_plan_covariance_diag(self._h, ncol, var.ctypes.data, 0), "stmmqr_plan_covariance_diag")
         return var[:max(ncol, 0)]
 
+    def leverage(self, ncol=None, with_var=False, dev_ptr=None):
+        """The leverages of the rows, lev[i] = a_i' ((A E)_live' (A E)_live)^-1 a_i in the caller's row order (the diagonal of the hat
+        matrix; a_i: row i cut at ncol columns), read from the blocks of one selected inversion (stmmqr_plan_leverage).  with_var:
+        returns (lev, var) with var the bits of covariance_diag(ncol), from the same inversion.  dev_ptr: a device pointer that
+        receives the m doubles (returns None, or var alone with with_var)."""
+        ncol = self.sym["n"] if ncol is None else int(ncol)
+        m = self.sym["m"]
+        var = np.zeros(max(ncol, 1)) if with_var else None
+        vp = None if var is None else var.ctypes.data
+        if dev_ptr is not None:
+            if with_var:                                                     # (one call takes host or device pointers, not both)
+                raise StmmqrError("HipQR.leverage: with_var needs host output (dev_ptr=None)")
+            _check(lib.stmmqr_plan_leverage(self._h, ncol, C.c_void_p(int(dev_ptr)), None, 1), "stmmqr_plan_leverage")
+            return None
+        lev = np.zeros(max(m, 1))
+        _check(lib.stmmqr_plan_leverage(self._h, ncol, lev.ctypes.data, vp, 0), "stmmqr_plan_leverage")
+        return (lev[:m], var[:max(ncol, 0)]) if with_var else lev[:m]
+
+    def covariance_entries(self, I, J, ncol=None) -> np.ndarray:
+        """Z(I[p], J[p]) of Z = ((A E)_live' (A E)_live)^-1, column indices in the caller's order (stmmqr_plan_covariance_entries).
+        Every pair must lie in the pattern of the selected inverse (two columns that share a row of A always do): the first one
+        that does not raises StmmqrError (code -4) naming it."""
+        ncol = self.sym["n"] if ncol is None else int(ncol)
+        I = np.ascontiguousarray(I, I64).reshape(-1); J = np.ascontiguousarray(J, I64).reshape(-1)
+        if I.size != J.size:
+            raise StmmqrError("HipQR.covariance_entries: I and J must have the same length")
+        out = np.zeros(max(I.size, 1))
+        _check(lib.stmmqr_plan_covariance_entries(self._h, ncol, I.size, I.ctypes.data, J.ctypes.data, out.ctypes.data, 0),
+               "stmmqr_plan_covariance_entries")
+        return out[:I.size]
+
     def solve(self, B: np.ndarray) -> np.ndarray:
         """QR_solve(QR_RETX_EQUALS_B) (SparseQR.h:411-417): X = E R^-1 (Q'B)(1:n), least-squares solution; rank == n only."""
         m, n = self.sym["m"], self.sym["n"]
@@ -1003,6 +1036,8 @@ lib.stmmqr_ls_plan.argtypes = [C.c_void_p]
 lib.stmmqr_ls_info.argtypes = [C.c_void_p, c_double_p]
 lib.stmmqr_ls_resid.argtypes = [C.c_void_p, c_double_p]
 lib.stmmqr_ls_covariance_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+lib.stmmqr_ls_leverage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+lib.stmmqr_ls_covariance_entries.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_ls_free.restype = None
 lib.stmmqr_ls_free.argtypes = [C.c_void_p]
 
@@ -1094,6 +1129,34 @@ class LeastSquares:
         var = np.zeros(max(self.n, 1))
         _check(lib.stmmqr_ls_covariance_diag(self._h, var.ctypes.data, 0), "stmmqr_ls_covariance_diag")
         return var[:self.n]
+
+    def diagnostics(self):
+        """after solve(): (leverages, variances) from ONE selected inversion (stmmqr_ls_leverage): the leverages of the m rows of A
+        and the bits of variances()."""
+        lev, var = np.zeros(max(self.m, 1)), np.zeros(max(self.n, 1))
+        _check(lib.stmmqr_ls_leverage(self._h, lev.ctypes.data, var.ctypes.data, 0), "stmmqr_ls_leverage")
+        return lev[:self.m], var[:self.n]
+
+    def leverages(self, dev_ptr=None):
+        """after solve(): h_i = a_i' (A_live' A_live)^-1 a_i for the m rows of A, the diagonal of the hat matrix (0 <= h_i <= 1, their sum
+        is the rank).  dev_ptr: a device pointer that receives the m doubles (returns None)."""
+        if dev_ptr is not None:
+            _check(lib.stmmqr_ls_leverage(self._h, C.c_void_p(int(dev_ptr)), None, 1), "stmmqr_ls_leverage")
+            return None
+        lev = np.zeros(max(self.m, 1))
+        _check(lib.stmmqr_ls_leverage(self._h, lev.ctypes.data, None, 0), "stmmqr_ls_leverage")
+        return lev[:self.m]
+
+    def covariance(self, I, J) -> np.ndarray:
+        """after solve(): the entries (I[p], J[p]) of (A_live' A_live)^-1, A's column order; pairs outside the pattern of the selected
+        inverse are refused (stmmqr_ls_covariance_entries).  The correlation of x_i and x_j is cov(i, j) / sqrt(var_i var_j)."""
+        I = np.ascontiguousarray(I, I64).reshape(-1); J = np.ascontiguousarray(J, I64).reshape(-1)
+        if I.size != J.size:
+            raise StmmqrError("LeastSquares.covariance: I and J must have the same length")
+        out = np.zeros(max(I.size, 1))
+        _check(lib.stmmqr_ls_covariance_entries(self._h, I.size, I.ctypes.data, J.ctypes.data, out.ctypes.data, 0),
+               "stmmqr_ls_covariance_entries")
+        return out[:I.size]
 
     def std_errors(self) -> np.ndarray:
         """after solve(): the standard errors of x, n x nrhs: sqrt(var * resid_j^2 / (m - rank)) for right-hand side j; inf where

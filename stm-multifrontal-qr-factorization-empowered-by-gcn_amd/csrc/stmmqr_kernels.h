@@ -126,6 +126,15 @@ int stm_launch_carried_seed(double *X, long long ldx, int n, int j0, int nb, hip
 int stm_launch_si_prep(const DevCtx &c, int nf, const SiDesc *sd, int *Lc, int *Pos, int *Rm, int *err, hipStream_t st);
 int stm_launch_si_level(const DevCtx &c, const int *flist, int nfr, int max_r, int max_cn, const SiDesc *sd, const int *Rm, const int *Lc,
                         const int *Pos, const int *Rj, const int *Qfill, double *W, double *Z, double *var, hipStream_t st);
+// leverages and single entries of the selected inverse (stmmqr_leverage.hip), read from the blocks the level loop above leaves in Z.
+// SiView: what the lookups read besides DevCtx::fs -- colfront[k] = the front where column k (R's order, k < ncol) is pivotal
+struct SiView { const SiDesc *sd; const int *Pos; const int *Rj; const int *colfront; const double *Z; };
+// lev[i] = a_i' Z a_i for the m rows of the caller's matrix: row PLinv[i] of S (Sp, Sj: global columns in R's order, Sx), columns >= ncol
+// skipped; *err = 2 if a pair of a row's columns is not in the blocks
+int stm_launch_si_leverage(const DevCtx &c, const SiView &v, int m, int ncol, const int *PLinv, const int *Sp, const int *Sj,
+                           const double *Sx, double *lev, int *err, hipStream_t st);
+// out[p] = the block entry of trip[3 p ..] = (front, local column of the earlier column, local column of the later one)
+int stm_launch_si_entries(const DevCtx &c, const SiView &v, int npairs, const int *trip, double *out, hipStream_t st);
 // Q-apply / triangular solve on the resident factors
 // Several right-hand sides per launch (QR_qmult / QR_solve take blocks of them: qr_panel, SparseQR.c:1591-1706): every kernel of
 // these operations takes right-hand side blockIdx.y (or .z) of a BATCH -- the same workgroups, one set per vector, in the same

@@ -208,6 +208,26 @@ int stmmqr_ls_covariance_diag(stmmqr_ls *ls, double *var, int on_device)
     return stmmqr_plan_covariance_diag(ls->plan, ls->n, var, on_device);
 }
 
+// the refusals the diagnostics of a fit share (what = the entry point's name)
+static int ls_fit_ready(const stmmqr_ls *ls, const char *what)
+{
+    if (!ls) return stm_fail(STMMQR_ERR_INVALID, (std::string(what) + ": null object").c_str());
+    if (!ls->plan) return stm_fail(STMMQR_ERR_INVALID, (std::string(what) + ": the object holds the host half only (device = -2 at create)").c_str());
+    if (ls->nsolves < 1) return stm_fail(STMMQR_ERR_INVALID, (std::string(what) + ": no solve yet").c_str());
+    return 0;
+}
+// leverages of the rows of A (and, var non-NULL, the variances from the same selected inversion) / entries of (A_live' A_live)^-1
+int stmmqr_ls_leverage(stmmqr_ls *ls, double *lev, double *var, int on_device)
+{
+    if (int e = ls_fit_ready(ls, "stmmqr_ls_leverage")) return e;
+    return stmmqr_plan_leverage(ls->plan, ls->n, lev, var, on_device);
+}
+int stmmqr_ls_covariance_entries(stmmqr_ls *ls, stm_long npairs, const stm_long *I, const stm_long *J, double *out, int on_device)
+{
+    if (int e = ls_fit_ready(ls, "stmmqr_ls_covariance_entries")) return e;
+    return stmmqr_plan_covariance_entries(ls->plan, ls->n, npairs, I, J, out, on_device);
+}
+
 void stmmqr_ls_free(stmmqr_ls *ls) { delete ls; }
 
 }  // extern "C"
