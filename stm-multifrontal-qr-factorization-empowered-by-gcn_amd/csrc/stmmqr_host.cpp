@@ -1539,11 +1539,17 @@ int stmmqr_device_alloc(size_t bytes, void **ptr)
     return 0;
 }
 /* device-to-device copy, complete on return (after everything `hip_stream` -- may be NULL -- held before it); for callers that
- * implement a stmmqr_transport of their own on one GPU (tests) */
+ * implement a stmmqr_transport of their own on one GPU (tests).  With a stream the copy is a command OF that stream: what the
+ * library records on the stream after the transport's call (the event its compute stream waits for before it unpacks a panel
+ * message) then orders the copy's writes before the kernels that read them.  As a null-stream copy beside an empty stream that
+ * event carried no dependency on the copy, and the unpacking kernel now and then read the PREVIOUS message of a reused ring
+ * buffer (thread ranks on one GPU: a shared front wrong from one panel on, one run in two of the sharded tests). */
 int stmmqr_device_copy(void *dst, const void *src, size_t bytes, void *hip_stream)
 {
-    if (hip_stream) HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
-    if (bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice));
+    if (hip_stream) {
+        if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+        HIPCHK(hipStreamSynchronize((hipStream_t)hip_stream));
+    } else if (bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice));
     HIPCHK(hipDeviceSynchronize());
     return 0;
 }

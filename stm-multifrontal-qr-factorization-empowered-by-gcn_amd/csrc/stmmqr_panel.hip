@@ -624,12 +624,18 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
                                                const double *sigp = nullptr, int *abortp = nullptr)
 {
     const int tid = threadIdx.x;
-    const int m = num->fm, n = s.fn, npiv = s.fp;              // (fm is fixed before the panel kernels run)
+    const int m_ld = num->fm;                                  // (fm is fixed before the panel kernels run; settled before the column loop)
+    const int n = wave_uniform(s.fn), npiv = wave_uniform(s.fp);
     const long long ld = s.ld;
     const int k1 = p * STM_NB, k2 = min(n, k1 + STM_NB), nbp = k2 - k1;
     const int c0 = SWT * b, sw = min(SWT, nbp - c0);           // my columns: k1 + c0 + x, x < sw
     const int ns = (nbp + SWT - 1) / SWT;
+    // (the header values reach groups 1.. through per-lane loads: as scalars the row masks compare against a scalar)
+    g1 = wave_uniform(g1); tmax = wave_uniform(tmax);
     const int rb = g1;                                         // first row of the register image
+    // magnitude guard (stm_larfg_guarded): constant for the whole factorization, read through the scalar cache here so that the
+    // column steps find it in scalar registers (as a per-lane load issued before the loop it was waited for in every step)
+    const double sg = sigp ? ld_uniform_const(sigp) : 1.0, isg = sigp ? ld_uniform_const(sigp + 1) : 1.0;
     int par = 0;
     if (tid < SWT) ps.stair[tid] = (tid < sw) ? St[k1 + c0 + tid] : 0;     // (only this group ever writes these)
 #ifdef STMMQR_STAMPS
@@ -725,7 +731,9 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
             for (int r = 0; r < RPT; r++) {
                 const int i = rb + tid + NTH * r;
                 const double val = vc[min(i, tmax - 1)];       // (rows beyond a column's staircase are zero in F)
-                v[q][r] = (!live || i < d || i >= tmax) ? 0.0 : ((i == d) ? 1.0 : val);
+                // (the unit diagonal d < rb + STM_NB <= rb + NTH lies in the rows r == 0: below them one compare is enough)
+                if (r == 0) v[q][r] = (!live || i < d || i >= tmax) ? 0.0 : ((i == d) ? 1.0 : val);
+                else v[q][r] = (i < (live ? tmax : 0)) ? val : 0.0;
             }
         }
 #ifdef STMMQR_STAMPS
@@ -848,15 +856,22 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
         ch_g = ld_agent(&num->g); ch_rank = ld_agent(&num->rank); ch_pt = ld_agent(&pd->pt);
         ch_nl = ld_agent(&pd->nlive); ch_ls = ld_agent(&pd->lensum); ch_fl = (b == 0) ? num->flops : ld_agent(&num->flops);
     }
-    int g = (b == 0) ? g1 : ch_g;
-    int rank = ch_rank, done = prev_done, nlive = 0;
-    int tlast = (b == 0) ? g1 : ch_pt;
-    const int nl_before = (b == 0) ? 0 : ch_nl;
-    const double ls_before = (b == 0) ? 0.0 : ch_ls;
+    // Everything the column steps read from global memory is settled HERE, as wave-uniform scalars: no column step waits for
+    // memory.  (A wait for a load also drains the write-through stores that retired the previous column -- the memory counter
+    // counts both -- and a step that may be skipped leaves a load pending for the steps after it: the per-lane loads of sg, m
+    // and g were waited for at the head of every column.)  g, t, done and dead are scalars, so the bookkeeping of a step is
+    // scalar arithmetic and its branches are scalar branches.
+    prev_done = wave_uniform(prev_done);
+    const int m = wave_uniform(m_ld);
+    int g = wave_uniform((b == 0) ? g1 : ch_g);
+    int rank = wave_uniform(ch_rank), done = prev_done, nlive = 0;
+    int tlast = wave_uniform((b == 0) ? g1 : ch_pt);
+    const int nl_before = wave_uniform((b == 0) ? 0 : ch_nl);
+    const double ls_before = wave_uniform((b == 0) ? 0.0 : ch_ls);
+    ch_fl = wave_uniform(ch_fl);
     long long iflops = 0, ilen = 0;                            // the reference's flop count: integers, exact in fp64
     const int gs = g;
-    const int ntol = min(ntol_global - s.col1, npiv);
-    const double sg = sigp ? sigp[0] : 1.0, isg = sigp ? sigp[1] : 1.0;      // magnitude guard (stm_larfg_guarded)
+    const int ntol = wave_uniform(min(ntol_global - s.col1, npiv));
     // HStair / HTau / pdiag / Rdead of my columns [j0, j1): from LDS to global memory, write-through, before a publish
     auto flush_cols = [&](int j0, int j1) {
         lds_barrier();
@@ -894,14 +909,17 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
             // Straight-line column step: the dead-column and tau == 0 cases are folded into the scalars (a branch
             // around the update would make the compiler copy the whole register image at the join).
             TCY(0);
-            const int t = max(g + 1, ps.stair[j]);
+            const int t = max(g + 1, wave_uniform(ps.stair[j]));
             double part[8], sum[8];
 #pragma unroll
             for (int x = 0; x < 8; x++) part[x] = 0;
+            // Rows r >= 1 need no mask: g - rb < STM_NB <= NTH puts them below the diagonal, and their entries of column j at
+            // rows >= t are zero in the register image (F is zero beyond the non-decreasing staircase, the earlier reflectors end
+            // at or before t, the load zeroed the rows >= tmax) -- a zero contributes to the sums what the masked term did.
 #pragma unroll
             for (int r = 0; r < RPT; r++) {
                 const int i = rb + tid + NTH * r;
-                const double xv = (i > g && i < t) ? a[r][j] * sg : 0.0;   // (one operand carries the magnitude guard)
+                const double xv = (r > 0 || (i > g && i < t)) ? a[r][j] * sg : 0.0;   // (one operand carries the magnitude guard)
 #pragma unroll
                 for (int x = j; x < SWT; x++) part[x - j] += xv * a[r][x];
             }
@@ -921,7 +939,7 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
             stm_larfg_guarded(alpha, ss, sg, isg, bb, tau0, scal0, scals0);
             const bool ident = (ss == 0.0);
             const double beta = ident ? alpha : bb;
-            const bool dead = (k < ntol) && (fabs(beta) <= tol);    // (:1495-1544) column zeroed, g does not advance
+            const bool dead = wave_uniform((k < ntol) && (fabs(beta) <= tol));    // (:1495-1544) column zeroed, g does not advance
             const bool upd = !ident && !dead;
             const double tau = upd ? tau0 : 0.0;
             const double scal = upd ? scal0 : 0.0, scals = upd ? scals0 : 0.0;
@@ -932,8 +950,8 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
 #pragma unroll
             for (int r = 0; r < RPT; r++) {
                 const int i = rb + tid + NTH * r;
-                const bool act = (i > g && i < t);
-                const double v = act ? a[r][j] * scal : 0.0;    // (upd false: the entries are zero already, or dead)
+                const bool act = (r > 0 || (i > g && i < t));   // (r >= 1: a zero beyond t stays a zero, as above)
+                const double v = act ? a[r][j] * scal : 0.0;    // (upd false: scal = 0 -- the entries are zero already, or dead)
                 a[r][j] = act ? v : ((dead && i >= g) ? 0.0 : a[r][j]);
 #pragma unroll
                 for (int x = j + 1; x < SWT; x++) a[r][x] -= w[x - j] * v;
@@ -949,7 +967,7 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
             if (!dead) {
                 iflops += (long long)(t - g) * (3 + 4 * (long long)(n - k - 1));
                 ilen += (t - g);
-                nlive += (tau != 0.0);
+                nlive += wave_uniform(tau != 0.0);
                 tlast = t;
                 g++;
             }
@@ -1063,7 +1081,7 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
     constexpr int NTH = 64 * (STM_NB / SW), RS = 64 * RPT;
     static_assert(SW == 4 || SW == 8, "a wave takes 4 or 8 columns");
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int m = num->fm, n = s.fn, npiv = s.fp;
+    const int m_ld = num->fm, n = wave_uniform(s.fn), npiv = wave_uniform(s.fp);      // (m: settled before the columns, below)
     const long long ld = s.ld;
     const int k1 = p * STM_NB, k2 = min(n, k1 + STM_NB), nbp = k2 - k1;
     const int c0 = SW * w, sw = max(0, min(SW, nbp - c0));
@@ -1093,8 +1111,11 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
     auto wait_col = [&](int j) {
         while (__hip_atomic_load(&wsh.ready[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
     };
-    const int ntol = min(ntol_global - s.col1, npiv);
-    const double sg = sigp ? sigp[0] : 1.0, isg = sigp ? sigp[1] : 1.0;
+    // (as in dev_tall_group: what the column steps read from global memory is in scalar registers before they start, and
+    //  g, t, done and dead are scalars -- no step waits for memory, which would also drain the stores of the column before it)
+    const int ntol = wave_uniform(min(ntol_global - s.col1, npiv));
+    const double sg = sigp ? ld_uniform_const(sigp) : 1.0, isg = sigp ? ld_uniform_const(sigp + 1) : 1.0;
+    const int m = wave_uniform(m_ld);
     if (sw > 0) {
         // ---- the reflectors of the waves before mine, one dlarf each, as they appear ----
         for (int j = 0; j < c0; j++) {
@@ -1110,7 +1131,7 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
             for (int r = 0; r < RPT; r++) {
                 const int i = rb + lane + 64 * r;
                 const double val = vs[lane + 64 * r];           // (rows beyond a column's staircase are zero)
-                v[r] = (i < d) ? 0.0 : ((i == d) ? 1.0 : val);
+                v[r] = (r > 0) ? val : (i < d) ? 0.0 : ((i == d) ? 1.0 : val);     // (d < rb + STM_NB <= rb + 64: the rows r == 0)
 #pragma unroll
                 for (int x = 0; x < SW; x++) pv[x] += v[r] * a[r][x];
             }
@@ -1129,7 +1150,8 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
             }
         }
         if (c0 > 0) wait_col(c0 - 1);                            // (a skipped reflector above was still waited for)
-        int g = wsh.g, rank = wsh.rank, done = wsh.done, tlast = wsh.tlast, nlive = wsh.nlive, jdone = wsh.jdone;
+        int g = wave_uniform(wsh.g), rank = wave_uniform(wsh.rank), done = wave_uniform(wsh.done), tlast = wave_uniform(wsh.tlast);
+        int nlive = wave_uniform(wsh.nlive), jdone = wave_uniform(wsh.jdone);
         long long iflops = wsh.iflops, ilen = wsh.ilen;
         // ---- my columns ----
 #pragma unroll
@@ -1148,14 +1170,15 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
                 jdone = jp;
             }
             if (!done) {
-                const int t = max(g + 1, ps.stair[jp]);
+                const int t = max(g + 1, wave_uniform(ps.stair[jp]));
                 double part[8];
 #pragma unroll
                 for (int e = 0; e < 8; e++) part[e] = 0.0;
 #pragma unroll
                 for (int r = 0; r < RPT; r++) {
                     const int i = rb + lane + 64 * r;
-                    const double xv = (i > g && i < t) ? a[r][x] * sg : 0.0;   // (one operand carries the magnitude guard)
+                    // (rows r >= 1 lie below the diagonal, and column x is zero there from row t on: dev_tall_group)
+                    const double xv = (r > 0 || (i > g && i < t)) ? a[r][x] * sg : 0.0;   // (one operand carries the magnitude guard)
 #pragma unroll
                     for (int y = x; y < SW; y++) part[y - x] += xv * a[r][y];
                 }
@@ -1178,7 +1201,7 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
                 stm_larfg_guarded(alpha, ss, sg, isg, bb, tau0, scal0, scals0);
                 const bool ident = (ss == 0.0);
                 const double beta = ident ? alpha : bb;
-                const bool dead = (k < ntol) && (fabs(beta) <= tol);    // (:1495-1544) column zeroed, g does not advance
+                const bool dead = wave_uniform((k < ntol) && (fabs(beta) <= tol));    // (:1495-1544) column zeroed, g does not advance
                 const bool upd = !ident && !dead;
                 const double tau = upd ? tau0 : 0.0;
                 const double scal = upd ? scal0 : 0.0, scals = upd ? scals0 : 0.0;
@@ -1188,7 +1211,7 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
 #pragma unroll
                 for (int r = 0; r < RPT; r++) {
                     const int i = rb + lane + 64 * r;
-                    const bool act = (i > g && i < t);
+                    const bool act = (r > 0 || (i > g && i < t));
                     const double v = act ? a[r][x] * scal : 0.0;
                     a[r][x] = act ? v : ((dead && i >= g) ? 0.0 : a[r][x]);
 #pragma unroll
@@ -1206,7 +1229,7 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
                 if (!dead) {
                     iflops += (long long)(t - g) * (3 + 4 * (long long)(n - k - 1));
                     ilen += (t - g);
-                    nlive += (tau != 0.0);
+                    nlive += wave_uniform(tau != 0.0);
                     tlast = t;
                     g++;
                 }

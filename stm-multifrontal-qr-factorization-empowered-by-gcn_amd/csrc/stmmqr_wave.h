@@ -95,6 +95,23 @@ __device__ __forceinline__ double wave_reduce8(const double (&v)[8])
     return wave_sum_stride8(wave_reduce8_partial(v));
 }
 
+// A value that is the same in every lane although the compiler cannot prove it (loaded by every lane from one address,
+// computed by every lane from the same operands), moved to scalar registers: what depends on it becomes scalar arithmetic
+// and scalar branches, and a load it comes from is settled where the move stands.  (Only where that holds: the int and double
+// forms return the first active lane's value, the bool form whether any active lane has it set.)
+__device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double wave_uniform(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+__device__ __forceinline__ bool wave_uniform(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0; }
+// Load of a double that nothing writes while the kernel runs, through the scalar cache into scalar registers (the
+// constant address space: the address must be wave-uniform).
+__device__ __forceinline__ double ld_uniform_const(const double *p)
+{
+    return *(const __attribute__((address_space(4))) double *)(unsigned long long)p;
+}
+
 // value of lane SRC (compile-time) in every lane, as a wave-uniform value
 template <int SRC>
 __device__ __forceinline__ double lane_bcast(double v)
