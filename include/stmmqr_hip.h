@@ -108,7 +108,7 @@ stm_qr_numeric *qr_factorize(stm_sparse_csc **Ahandle, stm_long freeA, double to
  * expensive to build as one factorization of the BASELINE matrices): a later call with an EQUAL qr_symbolic -- compared by a hash of
  * its scalars and arrays, the options and the plan-time environment -- and the same device reuses it, and skips the value map
  * (qr_stranspose2) too when A's pattern is unchanged.  A cached plan keeps its device memory until stmmqr_plan_cache_clear() /
- * stmmqr_shutdown(); env STMMQR_PLAN_CACHE = 0 turns the cache off, = n keeps the n most recent plans (default 1).
+ * stmmqr_shutdown(); env STMMQR_PLAN_CACHE = 0 turns the cache off, = n keeps the n most recent plans.
  * STMMQR_SEAM_TIMING=1 prints where a call spent its time.  Match: the interval SparseQR.c:346-377 brackets ("Factorize time"). */
 void stmmqr_plan_cache_clear(void);
 /* releases a qr_numeric returned by qr_factorize with the reference's accounting (= qr_freenum, SparseQR.c:1225-1272), for hosts
@@ -481,25 +481,18 @@ double stmmqr_last_seam_ms(void);
  * measured slower at every setting: mid_front_cols = whole mid-size fronts in one workgroup, pair_update = 2 = the single-sweep pair
  * update; profiles/EXPERIMENTS.md.)   Read when a plan is created (or a seam is called); the numerical results do not
  * depend on them beyond rounding.
- * Environment (diagnosis, tests and experiments only; read at plan time unless noted): STMMQR_DBG (bit mask,
- * csrc/stmmqr_kernels.h), STMMQR_QBIG_MIN (entries of a front from which Q-apply / back substitution split its rows over
- * workgroups; default 2097152), STMMQR_CHUNK (fronts per panel launch with STMMQR_DBG bit 9), STMMQR_SCHED (step order:
- * 1 level-synchronous, 2 as soon as possible, 3 envelope rule; unset: chosen per front group), STMMQR_RIDE (envelope rule:
- * factor on the height a riding front may have), STMMQR_CA_MIN (rows from which the Gram-based panel is used; 4096),
- * STMMQR_PAIR_MIN (rows from which a front takes the pair update; 16384), STMMQR_LA_MIN / STMMQR_LA_MAXPWG (look-ahead:
- * tiles of trailing update from which a step is offloaded, 2500, and the most panel workgroups such a step may have, 48;
- * read per factorization), STMMQR_SIDE_RESERVE (compute units the side stream leaves alone; 32), STMMQR_DUMPSTEPS=file
- * (detail runs: one line per step with what ran and how long); STMMQR_DBG bits of general use: 16 diagnosis counters printed
- * by stmmqr_factorize_finish (panels by actual rows, launched / useful update workgroups, refresh rounds), 16384 no
- * wave-pipelined panels (every short panel through the multi-workgroup pipeline).
- * Round 5: STMMQR_EARLY_END=0 (every panel of every front a step of the timeline; default: a front is scheduled up to the panel
- * where the full-rank row estimate says it runs out of rows) and STMMQR_EARLY_SLACK (extra panels per front, 0);
- * STMMQR_PASSENGERS=0 / STMMQR_PASS_ROWS (16384) / STMMQR_PASS_MAXWG (384) / STMMQR_CA_RIDERS=0 (passenger launches: off, the rows
- * up to which a step rides, the workgroups of its block-0 launch, riders on the Gram-based panel launch); STMMQR_PART_GRAIN / _CAP
- * (entries per workgroup, 2048, and workgroups per front, 4096, of the assembly / packing launches); STMMQR_LIVE_PANELS=0 (Q-apply /
- * back substitution visit every panel, not only those that can hold a reflector); STMMQR_RHS_BATCH (right-hand sides per pass of
- * the resident-factor operations, 32); STMMQR_NATIVE_PHASES=0 and STMMQR_EARLY_END_SHARDED=0 (sharded.py: the Python phase loop;
- * the full schedule on sharded plans). */
+ * Environment (diagnosis, tests and experiments only): every STMMQR_* variable the library reads is one row of the table in
+ * csrc/stmmqr_knobs.h, with its default, its reading rule and the moment it is read.  Those a caller may reasonably set:
+ * STMMQR_PLAN_CACHE (plans the drop-in seam keeps; 0 turns the cache off) and STMMQR_SEAM_TIMING=1 (section 1); STMMQR_RECYCLE
+ * (slab recycling: 0 never, 2 always; unset: by the size of the fronts); STMMQR_EARLY_END=0 (every panel of every front a step of
+ * the timeline; default: a front is scheduled up to the panel where the full-rank row estimate says it runs out of rows,
+ * DESIGN.md 4); STMMQR_PASSENGERS=0 (passenger launches off); STMMQR_RHS_BATCH (right-hand sides per pass of the resident-factor
+ * operations); STMMQR_RESIDENT_CACHE (recycled slabs: every front in front form at once, 1, or level by level, 0); STMMQR_MEMDUMP=1
+ * (device memory by purpose); STMMQR_DUMPSTEPS=file (detail runs: one line per step with what ran and how long); STMMQR_DBG (bit
+ * mask, csrc/stmmqr_kernels.h; of general use: 16 diagnosis counters printed by stmmqr_factorize_finish -- panels by actual rows,
+ * launched / useful update workgroups, refresh rounds --, 16384 no wave-pipelined panels: every short panel through the
+ * multi-workgroup pipeline).  The Python package adds STMMQR_NATIVE_PHASES=0 and STMMQR_EARLY_END_SHARDED=0 (sharded.py: the
+ * Python phase loop; the full schedule on sharded plans). */
 typedef struct stmmqr_options {
     int panel_width;        /* Householder panel width on device (<= 32); reference FCHUNK = 32                    */
     int big_front_cols;     /* fronts with fn >= this use the multi-workgroup panel/update path                     */
@@ -507,7 +500,7 @@ typedef struct stmmqr_options {
     int use_graph;          /* replay the level schedule as a hipGraph (captured per plan and tol); 0: no gain measured */
     int panel_algo;         /* panel of the large fronts: 1 the column pipeline (one workgroup reduction per column),
                                2 the Gram-based panel (one Gram matrix per panel, any height), 0 (default) by the panel's
-                               estimated rows: Gram-based above 4096 (STMMQR_CA_MIN), the column pipeline below -- whose
+                               estimated rows: Gram-based above STMMQR_CA_MIN, the column pipeline below -- whose
                                panels of at most 512 actual rows are taken by ONE workgroup, a wave per 4 columns     */
     int split_update;       /* row-parallel (2-launch) trailing update for fronts of >= 3 row slabs (1)             */
     int tall_min_rows;      /* panels with more rows than this run as a pipeline of column groups (plan time; 0)    */
@@ -522,8 +515,8 @@ typedef struct stmmqr_options {
                                sums: DESIGN.md 5), kept as an experiment.  ONE exception to "0 = two launches": an offloaded
                                look-ahead step applies T + column block 0 in one fused launch when every workgroup of that launch
                                fits the compute units the side stream leaves alone (counted with the fronts' row BOUNDS) and the
-                               panels are expected to reach at most STMMQR_LA_FUSED_ROWS rows (5120; 0 turns it off).      */
-    int pair_update;        /* fronts of >= 16384 rows apply the block reflectors of several consecutive panels in ONE sweep over
+                               panels are expected to reach at most STMMQR_LA_FUSED_ROWS rows (0 turns it off).            */
+    int pair_update;        /* fronts of STMMQR_PAIR_MIN rows apply the block reflectors of several consecutive panels in ONE sweep over
                                the columns beyond the next panel (their update is bound by what a sweep moves per MFMA):
                                4 (default): four panels per sweep (k_upd_wq / k_upd_yq / k_upd_cq: 0.75 passes over the trailing
                                matrix per panel; round 4: configs[4] stand-in 4127 -> 3640 ms against pairs);

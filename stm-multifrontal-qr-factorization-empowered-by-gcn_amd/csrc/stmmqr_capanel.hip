@@ -35,6 +35,7 @@
 #include "stmmqr_wave.h"
 #include "stmmqr_devutil.h"
 #include "stmmqr_riders.h"
+#include "stmmqr_knobs.h"
 
 #define CA_NT 512
 #define CA_LD (STM_CA_R + 2)      // column stride of the slab image (doubles): = 2 mod 32, MFMA operand reads conflict free
@@ -570,8 +571,7 @@ int stm_launch_panel_ca_pc(const DevCtx &c, const int *flist, const int *plist, 
     const int n0 = nfr < K ? nfr : K;
     int rspw = 1;
     {
-        static int force = -1;
-        if (force < 0) force = getenv("STMMQR_RSPW") ? atoi(getenv("STMMQR_RSPW")) : 0;
+        const int force = (int)knobs::once<knobs::K_RSPW>();
         double best = 1e30;
         for (int k = 1; k <= 16; k *= 2) {
             const long wgs = (long)unfr * uncb * ((umaxsl + k - 1) / k);

@@ -26,7 +26,7 @@ struct FrontSym {
     int parent;              // parent front or -1
     int fm_est;              // rows of F if no pivot column dies (exact for full-rank fronts): launch planning only
     int tpan;                // index of this front's first panel in the kept-T array (DevCtx::Tall), panel p at tpan + p
-    int nsched;              // panels of this front that get a step of the timeline (<= npanels: build_schedule, "how many panels")
+    int nsched;              // panels of this front that get a step of the timeline (<= npanels: stmmqr_schedule.cpp, "how many panels")
     int qbig;                // Q-apply on the resident factors: the rows of this front are split over workgroups, one launch
                              // per panel (k_qbig_*), instead of one workgroup for the whole front (plan time)
 };
@@ -147,8 +147,8 @@ static inline __host__ __device__ int stm_quad_slots(int nslf, int tune)
     if (tune >> 8) return stm_pair_slots(nslf, 0);               // (another 8-slab threshold, measurement sweeps: the pair's stride covers it)
     return nslf < 16 ? nslf : (nslf + 7) / 8 > 16 ? (nslf + 7) / 8 : 16;
 }
-#define STM_PAIR_MIN_ROWS 16384  // fronts with at least this many (estimated) rows take the pair update (stmmqr_options::pair_update);
-                                 // measured: 27 000 rows -12 %, 7818 rows +17 % (and no look-ahead for pair steps)
+// (fronts with at least STMMQR_PAIR_MIN estimated rows -- stmmqr_knobs.h -- take the pair update, stmmqr_options::pair_update;
+//  measured: 27 000 rows -12 %, 7818 rows +17 %, and no look-ahead for pair steps)
 
 // Dynamic LDS (bytes) that ONE right-hand side of a front needs in the one-workgroup kernels on the resident factors: k_qapply_t holds
 // the front's rows of x and the reflector numbering, k_rsolve the pivotal and non-pivotal parts of x and the live-column list.  A

@@ -95,7 +95,7 @@ int stm_launch_update_notrans(const DevCtx &c, int f, int ncb, hipStream_t st); 
 int stm_launch_cpack(const DevCtx &c, const int *flist, const int *nparts, int nfr, int maxparts, hipStream_t st);
 int stm_launch_rh_count(const DevCtx &c, const int *flist, int nfr, hipStream_t st);
 int stm_launch_rh_scan(const DevCtx &c, const int *post, int nf, long long *rh_total, long long *outoff, hipStream_t st);
-// slab recycling (stmmqr_host.cpp, timeline allocator)
+// slab recycling (stmmqr_schedule.cpp, timeline allocator)
 int stm_launch_zero_slabs(const DevCtx &c, const int *flist, int nfr, int maxparts, hipStream_t st);
 int stm_launch_rh_unpack(const DevCtx &c, const FrontSym *cs, const int *flist, int nfr, int maxparts, const char *kept, const double *RH,
                          double *scratch, hipStream_t st);

@@ -11,7 +11,7 @@ __device__ void dev_tlast(const DevCtx &c, int f, const FrontSym &s, FrontNum *n
     const int p = s.npanels - 1;
     if (p < 0) return;
     // a front whose schedule stopped before its last panel (FrontSym::nsched) must have run out of rows by now; if it has not,
-    // the host runs the factorization again on the full schedule (abort[2]; stmmqr_host.cpp, "how many panels")
+    // the host runs the factorization again on the full schedule (abort[2]; stmmqr_schedule.cpp, "how many panels")
     if (s.nsched < s.npanels) {
         if (threadIdx.x == 0 && !num->done && c.abort) c.abort[2] = 1;
         return;                                                // (the last panel never ran: nothing pending of it)
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(NT) void k_rh_count(DevCtx c, const int *__restrict
     if (tid == 0) {
         num->rsize = carry;
         if (c.rh_top) {
-            // slab recycling (stmmqr_host.cpp, "timeline allocator"): the block gets its place in the R+H arena NOW, by a device-side
+            // slab recycling (stmmqr_schedule.cpp, "timeline allocator"): the block gets its place in the R+H arena NOW, by a device-side
             // bump pointer -- its size depends on the numerical rank, the host never learns it before the end.  The arena holds
             // QRsym->maxstack doubles, the reference's own bound for all of R+H (SparseQR_analyze.c:1061-1161); should a block
             // not fit all the same, the overflow word is raised and nothing is copied (the host repeats without recycling).

@@ -3,6 +3,7 @@
 // dev_wave_panel (a wave per 4 columns), k_front_wg, k_panel, k_panel_pc (panel + k_upd_c riders).  Shared device code: stmmqr_kdev.h.
 #include "stmmqr_kdev.h"
 #include "stmmqr_riders.h"
+#include "stmmqr_knobs.h"
 
 
 // ------------------------------------------------------------------------------------------------
@@ -1515,7 +1516,7 @@ int stm_launch_panel(const DevCtx &c, const int *flist, const int *plist, int nf
     // Oversubscribed launches (more workgroups than the GPU holds: groups start late) are exercised by the tests;
     // STMMQR_DBG bit 9 + STMMQR_CHUNK launch the fronts in chunks instead (tests).
     int K = nfr;
-    if (nsub > 1 && (c.dbg & 512)) K = getenv("STMMQR_CHUNK") ? atoi(getenv("STMMQR_CHUNK")) : 1;
+    if (nsub > 1 && (c.dbg & 512)) K = (int)knobs::num(knobs::K_CHUNK);
     if (K < 1) K = 1;
     for (int i = 0; i < nfr; i += K)
         hipLaunchKernelGGL(k_panel, dim3(nfr - i < K ? nfr - i : K, nsub), dim3(NTP), bytes, st, c, flist + i, plist + i, nsub, defer_ok,
@@ -1545,8 +1546,7 @@ int stm_launch_panel_pc(const DevCtx &c, const int *flist, const int *plist, int
     // chain and prologue (~5 us) overlap with nothing; per slab ~2.4 us.  Rounds of ~240 workgroups (urows: the launch's tiles, a bound)
     int rspw = 1;
     {
-        static int force = -1;
-        if (force < 0) force = getenv("STMMQR_RSPW") ? atoi(getenv("STMMQR_RSPW")) : 0;
+        const int force = (int)knobs::once<knobs::K_RSPW>();
         double best = 1e30;
         for (int k = 1; k <= 16; k *= 2) {
             const long wgs = (long)unfr * uncb * ((umaxsl + k - 1) / k);

@@ -1,5 +1,7 @@
 // stmmqr_plan.h -- the plan object and the helpers shared by the host translation units of libstmmqr_hip.so (local to the library):
-//   stmmqr_host.cpp      planner, step scheduler, factorization entry points, download
+//   stmmqr_host.cpp      device set-up, the symbolic plan, factorization entry points, download
+//   stmmqr_schedule.cpp  arenas, the timeline allocator, the step timeline of every front group (stm_build_schedule)
+//   stmmqr_run.cpp       the step scheduler (stm_run_schedule: one step, serial, look-ahead, passengers), the pack pass
 //   stmmqr_multi.cpp     contribution blocks / panels in and out of a plan, shared fronts, the RCCL transport
 //   stmmqr_rfactor.cpp   Q-apply and triangular solves on the resident factors
 //   stmmqr_seam.cpp      the drop-in seam qr_factorize with the reference's structs, its plan cache
@@ -25,6 +27,7 @@
 #include "stmmqr_device.h"
 #include "stmmqr_kernels.h"
 #include "stmmqr_internal.h"
+#include "stmmqr_knobs.h"
 
 
 extern thread_local std::string g_err;
@@ -49,6 +52,8 @@ int fail(int code, const std::string &msg);
         int e_ = (expr);                                                                                  \
         if (e_ != 0) return fail(STMMQR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString((hipError_t)e_)); \
     } while (0)
+
+#define PASS(expr) do { int e_ = (expr); if (e_ != 0) return e_; } while (0)      // (the callee has said why)
 
 inline double now_ms()
 {
@@ -134,7 +139,7 @@ struct stmmqr_plan {
     int do_rank = 1;
     int keep_h = 1;                                    // QRsym->keepH: 0 = the packed blocks hold R only (qr_rhpack's keepH = 0 layout);
                                                        //  no Q-apply, one group only (stmmqr_plan_set_groups refuses)
-    int ca_min = STM_CA_MIN_ROWS;                      // (env STMMQR_CA_MIN at plan time: experiments)
+    int ca_min = STM_CA_MIN_ROWS;                      // (env STMMQR_CA_MIN when the schedule was built: experiments)
     int plan_algo = 0;                                 // g_opt.panel_algo when the schedule was built
     int tall_min = STM_TALL_MIN;                       // g_opt.tall_min_rows when the schedule was built
     int tune = 0;                                      // env STMMQR_TUNE when the schedule was built (measurement sweeps)
@@ -263,8 +268,8 @@ struct stmmqr_plan {
     long long xf_doubles = 1, wq_doubles = 1;
     std::vector<QbLevel> level_qbig;               // descriptors (d_qb) of the fronts of each level that take the split Q-apply
     hipGraphExec_t graph_exec = nullptr;           // options.use_graph: the captured schedule of group 0
-    double graph_tol = 0; int graph_ntol = 0, graph_dbg = 0; long long graph_opt = 0; long graph_nlaunch = 0;
-    long sched_gen = 0, graph_gen = -1;            // schedule generation (bumped by every build_schedule) / the captured one
+    double graph_tol = 0; int graph_ntol = 0, graph_dbg = 0; unsigned long long graph_opt = 0; long graph_nlaunch = 0;
+    long sched_gen = 0, graph_gen = -1;            // schedule generation (bumped by every stm_build_schedule) / the captured one
     bool rowmap_ready = false;         // d_Wmap belongs to the factorization currently held
     std::vector<int> level_lds_qa, level_lds_qa_all, level_lds_rs;   // dynamic LDS of k_qapply(_t) / k_rsolve per level of group 0
                                                                      // (_all: the unblocked kernel takes the split fronts too)
@@ -286,7 +291,8 @@ struct stmmqr_plan {
         add(d_fs_car); add(d_fnum_car); add(d_carlist); add(d_carN);
         return b;
     }
-    DevCtx ctx() const
+    DevCtx ctx() const { return ctx((int)knobs::num(knobs::K_DBG)); }
+    DevCtx ctx(int dbg) const                                     // (dbg: STMMQR_DBG as the caller has read it)
     {
         DevCtx c;
         c.fs = d_fs.p; c.fnum = d_fnum.p; c.Farena = d_F.p; c.Carena = d_C.p; c.Tws = d_T.p; c.tslot = d_tslot.p;
@@ -296,7 +302,7 @@ struct stmmqr_plan {
         c.Child = d_Child.p; c.Rjrel = d_Rjrel.p; c.Stair = d_Stair.p; c.Tau = d_Tau.p; c.Hii = d_Hii.p;
         c.Rdead = d_Rdead.p; c.Cmap = d_Cmap.p; c.Cursor = d_Cursor.p; c.Rhoff = d_Rhoff.p; c.Rboff = d_Rboff.p;
         c.tol = last_tol; c.ntol = (int)last_ntol;
-        c.dbg = getenv("STMMQR_DBG") ? atoi(getenv("STMMQR_DBG")) : 0;
+        c.dbg = dbg;
         c.sweep = sweep;
         c.tune = tune;                                            // (env STMMQR_TUNE when the schedule was built)
         c.Ypend = d_Ypend.p; c.ypoff = d_ypoff.p;
@@ -324,8 +330,14 @@ struct stmmqr_plan {
 // One piece of one timeline step (stmmqr_factorize_step): what = STMMQR_STEP_* bits; the update takes the column blocks
 // cb_first, cb_first + cb_stride, ... (at most cb_count of them when cb_count >= 0) of the step's fronts.
 struct StepReq { int step, what, cb_first, cb_stride, cb_count; };
-// planner / scheduler entry points used by the other host translation units (stmmqr_host.cpp)
+// planner (stmmqr_schedule.cpp) and scheduler (stmmqr_run.cpp) entry points used by the other host translation units
+void stm_assign_arenas(stmmqr_plan &P);
+int stm_ensure_arenas(stmmqr_plan &P);
+void stm_build_schedule(stmmqr_plan &P, std::vector<int> &tslot);
+int stm_upload_recycle(stmmqr_plan &P);
 int stm_run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req);
+int stm_run_pack(stmmqr_plan &P, bool &overflow);
+int stm_ensure_la_events(stmmqr_plan &P, size_t nsteps, const knobs::RunKnobs &k);
 int stm_ensure_device(int device);
 int stm_ensure_a_index(stmmqr_plan &P);
 extern "C" int stm_check_c_slot(const stmmqr_plan &P, stm_long f, long long csize, const char *what);     // (defined inside the C ABI block)

@@ -9,7 +9,6 @@
 // ---------------------------------------------------------------------------------------------
 namespace {
 // a callee's own refusal goes up as it is (LCHK is for HIP error codes and would re-label it)
-#define PASS(expr) do { int e_ = (expr); if (e_ != 0) return e_; } while (0)
 
 // Slab recycling: the resident-factor kernels read fronts in front form.  A front whose slab was recycled is put back into
 // that form, level by level, in a scratch that holds the widest tree level (res_ctx: the FrontSym array whose offsets point into
@@ -48,8 +47,8 @@ int ensure_scratch(stmmqr_plan &P)
     HIPCHK(hipMemGetInfo(&freeb, &totalb));
     long long all = 0;
     for (long f = 0; f < P.nf; f++) if (!P.kept[(size_t)f]) all += (long long)P.fs[f].ld * P.fs[f].fn;
-    const char *ev = getenv("STMMQR_RESIDENT_CACHE");
-    P.scr_all = ev ? atoi(ev) != 0 : (8.0 * (double)all <= 0.25 * (double)freeb);
+    const long cache = knobs::num(knobs::K_RESIDENT_CACHE);
+    P.scr_all = cache >= 0 ? cache != 0 : (8.0 * (double)all <= 0.25 * (double)freeb);
     if (P.scr_all) {
         long long o = 0;
         for (long f = 0; f < P.nf; f++)
@@ -214,10 +213,10 @@ int build_resident_tables(stmmqr_plan &P)
 // front of fm rows has fm live reflectors at most; they sit in its first fm + (dead pivot columns) columns, and a front has at
 // most fp - rank dead pivot columns.  The panels behind that column were launches that did nothing: on the default workload
 // 330 launches per Q'b, 177 of them for panels without a reflector (same finding as the factorization's own schedule,
-// stmmqr_host.cpp "how many panels").  STMMQR_LIVE_PANELS=0: every panel.
+// stmmqr_schedule.cpp "how many panels").  STMMQR_LIVE_PANELS=0: every panel.
 int count_live_panels(stmmqr_plan &P)
 {
-    const bool live = !(getenv("STMMQR_LIVE_PANELS") && atoi(getenv("STMMQR_LIVE_PANELS")) == 0);
+    const bool live = knobs::on(knobs::K_LIVE_PANELS);
     bool changed = false;
     for (size_t l = 0; l < P.level_qbig.size(); l++) {
         auto &Q = P.level_qbig[l];
@@ -293,13 +292,8 @@ RhsBatch rhs_strides(const stmmqr_plan &P)
     B.w = P.m; B.x = P.n; B.xf = P.xf_doubles; B.wq = P.wq_doubles; B.wq4 = std::max(1LL, P.wq4_doubles); B.u = std::max(1L, P.rjsize);
     return B;
 }
-// the largest batch the operations take in one pass (STMMQR_RHS_BATCH, default 32; 1: one vector after the other, as until round 4)
-int rhs_batch_max()
-{
-    static int v = -1;
-    if (v < 0) v = getenv("STMMQR_RHS_BATCH") ? std::max(1, atoi(getenv("STMMQR_RHS_BATCH"))) : 32;
-    return v;
-}
+// the largest batch the operations take in one pass (STMMQR_RHS_BATCH; 1: one vector after the other, as until round 4)
+int rhs_batch_max() { return (int)knobs::once<knobs::K_RHS_BATCH>(); }
 // op(j0, nb) for the right-hand sides j0 .. j0 + nb - 1, batch after batch: every launch of a pass over the tree carries a whole batch
 // (RhsBatch), and the per-vector buffers hold it before op runs
 template <class Op> int for_each_batch(stmmqr_plan &P, stm_long nrhs, Op op)
@@ -323,7 +317,7 @@ int run_qapply(stmmqr_plan &P, int method, int nb = 1)
     // to rounding: used by the tests to cross-check the two)
     const bool blocked = c.Tall && !(c.dbg & 8192);
     // grouped split Q-apply: its buffers at the first use (STMMQR_QT4=0: the per-panel launches)
-    const bool want_t4 = !(getenv("STMMQR_QT4") && atoi(getenv("STMMQR_QT4")) == 0);       // (read at every call: tests compare both)
+    const bool want_t4 = knobs::on(knobs::K_QT4);                                          // (read at every call: tests compare both)
     if (blocked && want_t4 && !P.t4_tried && !P.t4items.empty()) {
         P.t4_tried = true;
         size_t freeb = 0, totalb = 0;
@@ -341,7 +335,7 @@ int run_qapply(stmmqr_plan &P, int method, int nb = 1)
         }
     }
     const bool use_t4 = blocked && want_t4 && P.t4_ok;
-    if (use_t4 && getenv("STMMQR_MEMDUMP") && !P.t4_valid)
+    if (use_t4 && knobs::on(knobs::K_MEMDUMP) && !P.t4_valid)
         fprintf(stderr, "[stmmqr_hip] grouped Q-apply: T4 of %zu groups of %zu split fronts, %.3f GB (+ %.3f GB of slab partials)\n", P.t4items.size(),
                 P.t4fronts.size(), 8e-9 * (double)P.t4_doubles, 8e-9 * (double)P.wq4_doubles);
     auto launch = [&](size_t l, int m) -> int {

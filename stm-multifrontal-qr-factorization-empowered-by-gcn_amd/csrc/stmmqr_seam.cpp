@@ -118,12 +118,7 @@ unsigned long long symbolic_key(const stm_qr_symbolic *S)
     add(S->Post, S->nf); add(S->Hip, S->nf + 1); add(S->Fm, S->nf);
     h = hash_bytes(&g_opt, sizeof g_opt, h);
     // (every knob of the environment that is read when the plan / its schedule / its arenas are built)
-    for (const char *k : {"STMMQR_CA_MIN", "STMMQR_PAIR_MIN", "STMMQR_SCHED", "STMMQR_RIDE", "STMMQR_QBIG_MIN", "STMMQR_RECYCLE", "STMMQR_TUNE",
-                          "STMMQR_RH_EST_SCALE", "STMMQR_EARLY_END", "STMMQR_EARLY_SLACK", "STMMQR_PART_GRAIN", "STMMQR_PART_CAP"}) {
-        const char *v = getenv(k);
-        if (v) h = hash_bytes(v, strlen(v), h ^ 0x51ed);
-    }
-    return h;
+    return knobs::fold_plan_knobs(h);
 }
 struct CachedPlan { unsigned long long key = 0, pat = 0; stmmqr_plan *plan = nullptr; int device = -1; unsigned long tick = 0; };
 std::mutex g_cache_mu;
@@ -131,8 +126,7 @@ std::vector<CachedPlan> g_cache;
 unsigned long g_cache_tick = 0;
 int cache_capacity()
 {
-    const char *v = getenv("STMMQR_PLAN_CACHE");
-    return v ? std::max(0, atoi(v)) : 1;
+    return (int)knobs::num(knobs::K_PLAN_CACHE);
 }
 // take a plan for this key out of the cache (nullptr: none); the caller owns it until cache_put
 stmmqr_plan *cache_take(unsigned long long key, unsigned long long *pat)
@@ -206,7 +200,7 @@ static void prefault(void *p, size_t bytes)
 stm_qr_numeric *qr_factorize(stm_sparse_csc **Ahandle, stm_long freeA, double tol, stm_long ntol,
                              stm_qr_symbolic *S, stm_sparse_common *cc)
 {
-    const bool timing = getenv("STMMQR_SEAM_TIMING") != nullptr;
+    const bool timing = knobs::on(knobs::K_SEAM_TIMING);
     const double t_in = now_ms();
     if (!S) {                                                  // SparseQR_factorize.c:247-254
         if (freeA) cc_free_sparse(Ahandle, cc);
@@ -259,11 +253,12 @@ stm_qr_numeric *qr_factorize(stm_sparse_csc **Ahandle, stm_long freeA, double to
     double *early_stack = nullptr;
     size_t early_doubles = 0;
     std::thread early;
-    if (!st && !(getenv("STMMQR_SEAM_EARLY_ALLOC") && atoi(getenv("STMMQR_SEAM_EARLY_ALLOC")) == 0)) {
+    const long early_alloc = knobs::num(knobs::K_SEAM_EARLY_ALLOC);
+    if (!st && early_alloc != 0) {
         // (a first call has only QRsym->maxstack to go by -- about twice the packed factors on the BASELINE matrices -- and
         //  populating that much beside the factorization costs more than it saves: the helper runs for cached plans only,
         //  STMMQR_SEAM_EARLY_ALLOC=2 forces it for first calls too)
-        const bool force = getenv("STMMQR_SEAM_EARLY_ALLOC") && atoi(getenv("STMMQR_SEAM_EARLY_ALLOC")) == 2;
+        const bool force = early_alloc == 2;
         early_doubles = (cached && P->rh_total > 0) ? (size_t)((double)P->rh_total * 1.02) + 1024
                                                     : (force ? (size_t)std::max<stm_long>(S->maxstack, 1) : 0);
         if (early_doubles * sizeof(double) >= (64u << 20)) {

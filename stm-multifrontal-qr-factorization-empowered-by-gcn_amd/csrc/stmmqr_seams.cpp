@@ -18,6 +18,7 @@
 #include "stmmqr_device.h"
 #include "stmmqr_kernels.h"
 #include "stmmqr_internal.h"
+#include "stmmqr_knobs.h"
 
 extern "C" int stmmqr_device_count(void);
 
@@ -99,8 +100,8 @@ struct OneFront {
             c.sig = d_sig.p;
         }
         c.Stair = d_St.p; c.Tau = d_Tau.p; c.Rdead = d_Rdead.p; c.Rhoff = d_Rhoff.p; c.Rboff = d_Rboff.p;
-        c.dbg = getenv("STMMQR_DBG") ? atoi(getenv("STMMQR_DBG")) : 0;
-        c.tune = getenv("STMMQR_TUNE") ? atoi(getenv("STMMQR_TUNE")) : 0;
+        c.dbg = (int)knobs::num(knobs::K_DBG);
+        c.tune = (int)knobs::num(knobs::K_TUNE);
         { stmmqr_options o; stmmqr_get_options(&o); c.tall_min = o.tall_min_rows; c.panel_algo = o.panel_algo; c.ca_min_rows = STM_CA_MIN_ROWS; }
 #ifdef STMMQR_STAMPS
         if (!d_dbg.alloc(1024)) return false;
@@ -194,7 +195,7 @@ stm_long stmmqr_front(stm_long m, stm_long n, stm_long npiv, double tol, stm_lon
             const int defer_ok = (ncb > 0) ? 1 : 0;
             if (stm_use_ca(X.s, p, opt.panel_algo)) e = stm_launch_panel_ca(X.c, X.d_flist.p, d_pl.p + p, 1, stm_ca_slabs(X.s), defer_ok, nullptr);
             else {
-                // (as run_schedule: a short panel of the pipeline is taken by one workgroup with the panel's image in LDS)
+                // (as the planner's emit_steps: a short panel of the pipeline is taken by one workgroup with the panel's image in LDS)
                 const int lds = stm_tall_panel(X.s, p, X.c.tall_min) ? std::max(lds_for(m), STM_NB * STM_WP_ROWS) : lds_for(m);
                 e = stm_launch_panel(X.c, X.d_flist.p, d_pl.p + p, 1, stm_tall_launches(X.s, p, X.c.tall_min), defer_ok, lds, nullptr);
             }

@@ -17,7 +17,7 @@
 // the result is the reference's bit for bit (tests/test_symbolic.py: every sym_* array of every committed fixture).
 //
 // The task / stack decomposition of the reference's parallel analysis (:701-1161) has no counterpart here by design:
-// tree parallelism is the step scheduler's (stmmqr_host.cpp); the object says ntasks = ns = 1 like the
+// tree parallelism is the step scheduler's (stmmqr_run.cpp); the object says ntasks = ns = 1 like the
 // reference's own serial analysis (SPQR_grain <= 1).
 #include <algorithm>
 #include <cstdlib>

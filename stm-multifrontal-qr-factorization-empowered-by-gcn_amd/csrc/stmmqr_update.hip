@@ -3,6 +3,7 @@
 // riders (k_upd_b0w, k_upd_fw).  Shared device code: stmmqr_kdev.h.
 #include <hip/hip_ext.h>
 #include "stmmqr_kdev.h"
+#include "stmmqr_knobs.h"
 
 
 __global__ __launch_bounds__(NT) void k_update(DevCtx c, const int *__restrict__ flist, const int *__restrict__ plist, int cb0)
@@ -860,13 +861,11 @@ int stm_launch_update_fw(const DevCtx &c, const int *flist, const int *plist, in
 {
     if (nfr <= 0 || maxsl <= 0) return 0;
     const int rest = ncb - 1;
-    static int one = -1;
-    if (one < 0) one = getenv("STMMQR_B0_ONE") ? atoi(getenv("STMMQR_B0_ONE")) : 1;       // (0: k_upd_f with its two meeting points)
+    const int one = (int)knobs::once<knobs::K_B0_ONE>();                                // (0: k_upd_f with its two meeting points)
     if (one) {
         // slabs per rider workgroup: two (measured on the default workload: 1 slab 110.8 ms, 2 109.7, 4 110.1, 8 113.0 -- these riders
         // share their CU with a second workgroup, so less of a descriptor chain is exposed than in the panel launch)
-        static int rspw = -1;
-        if (rspw < 0) rspw = getenv("STMMQR_RSPW_W") && atoi(getenv("STMMQR_RSPW_W")) > 0 ? atoi(getenv("STMMQR_RSPW_W")) : 2;
+        const int rspw = (int)knobs::once<knobs::K_RSPW_W>();
         const int uy = (maxsl + rspw - 1) / rspw;
         hipLaunchKernelGGL(k_upd_b0w, dim3(maxsl > rest ? maxsl : rest, rest > 0 ? uy : 1, rest > 0 ? 2 * nfr : nfr), dim3(NT),
                            (size_t)stm_update_lds_bytes(), st, c, flist, plist, nfr, maxsl, rest > 0 ? rest : 0, Wp, wpoff, wcnt, wflag, epoch,
@@ -880,9 +879,7 @@ int stm_launch_update_fw(const DevCtx &c, const int *flist, const int *plist, in
 }
 static int stm_anyorder(void)
 {
-    static int v = -1;
-    if (v < 0) v = getenv("STMMQR_ANYORDER") ? atoi(getenv("STMMQR_ANYORDER")) : 0;
-    return v;
+    return (int)knobs::once<knobs::K_ANYORDER>();
 }
 // k_upd_w alone into the passengers' workspace (measurements: the riders as launches of their own)
 int stm_launch_update_w(const DevCtx &c, const int *flist, const int *plist, int nfr, int cb0, int ncb, int maxsl, double *Wp,
