@@ -386,11 +386,25 @@ int stmmqr_plan_rsolve(stmmqr_plan *plan, int system, const double *B, stm_long 
  *                                (the basic solution).  info (may be NULL): the largest |A'r| / (|A|_F (|A|_F |x| + |b|)) over the
  *                                right-hand sides, r = b - A x of the returned x.  Accurate to about cond(A) u only while
  *                                cond(A)^2 u << 1: above cond(A) ~ 1e7 the Q-based stmmqr_plan_solve is the right tool.  A front too
- *                                wide for the one-workgroup R' solve gives STMMQR_ERR_TOO_LARGE, as stmmqr_plan_rsolve systems 2-3. */
+ *                                wide for the one-workgroup R' solve gives STMMQR_ERR_TOO_LARGE, as stmmqr_plan_rsolve systems 2-3.
+ *                                (stmmqr_plan_solve_minnorm below has no such limit: its R' pass splits such fronts.) */
 int stmmqr_plan_keep_h(const stmmqr_plan *plan);
 int stmmqr_plan_spmv(stmmqr_plan *plan, int trans, const double *X, stm_long ldx, double *Y, stm_long ldy, stm_long nrhs, int on_device);
 int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int refine,
                                  int on_device, double *info);
+
+/* X (m x nrhs, ldx >= m) = Q * (R' \ B) (permuted != 0: B, n x nrhs, is in R's column order) or Q * (R' \ (E' B)) (permuted == 0):
+ * with the plan holding the factorization of M (m x n), the minimum-2-norm solution of the equations M(:, live)' x = b(live);
+ * live = the pivot columns that did not die.  Dead columns have no equation (the squeezed R of qr_private_rtsolve).
+ * Needs H.  on_device: B and X are device pointers.
+ * Everything runs on the device, with no host round trip between the two passes, and the result is in the caller's row order of M
+ * (what stmmqr_plan_qmult method 1 returns).  At default settings it is, bit for bit, stmmqr_plan_qmult(1) of stmmqr_plan_rsolve(3 / 2)
+ * wherever those accept the tree -- but it never returns STMMQR_ERR_TOO_LARGE for the width of a front: a front that the
+ * one-workgroup R' solve cannot hold has its columns split over workgroups (STMMQR_RTBIG_MIN splits smaller ones too).  Refusals
+ * (STMMQR_ERR_INVALID, the plan stays usable): nothing factorized, bad pointers or leading dimensions, keepH = 0 (the message names
+ * keepH, as stmmqr_plan_qmult's).  nrhs = 0 returns 0 and writes nothing. */
+int stmmqr_plan_solve_minnorm(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs,
+                              int permuted, int on_device);
 
 /* Least squares with the right-hand sides carried through the factorization: the plan holds a factorization of the m x (n + nrhs)
  * matrix [A B] made with ntol = n (the columns of B are never rank-tested), whose Qfill is the identity on the last nrhs columns.
@@ -601,6 +615,10 @@ int stmmqr_sparseqr_y(const stmmqr_qr *qr, const stm_long **Yp, const stm_long *
 int stmmqr_sparseqr_qmult(stmmqr_qr *qr, int method, const double *X, stm_long ldx, stm_long nrow, stm_long ncol, double *Y,
                           stm_long ldy);
 int stmmqr_sparseqr_solve(stmmqr_qr *qr, int system, const double *B, stm_long ldb, stm_long nrhs, double *X, stm_long ldx);
+/* On the QR object of A' (from stmmqr_sparselq, or stmmqr_sparseqr on the transpose): X (qr->m x nrhs) = the minimum-2-norm solution
+ * of A x = b for B (qr->n x nrhs), x = Q (R' \ (E' b)), singleton rows included (host arrays).  The multifrontal part is one
+ * stmmqr_plan_solve_minnorm call: no limit on the width of a front.  Needs H. */
+int stmmqr_sparseqr_min2norm(stmmqr_qr *qr, const double *B, stm_long ldb, stm_long nrhs, double *X, stm_long ldx);
 
 /* ---- R / H out in sparse form, LQ (STMMQR/src/qr/SparseLQ.c; prototypes SparseQR.h:282-340) ---------
  * qr_rcount / qr_rconvert / qr_trapezoidal keep the reference's names, argument lists and results (bit for bit: they move

@@ -150,6 +150,7 @@ lib.stmmqr_plan_keep_h.argtypes = [C.c_void_p]
 lib.stmmqr_plan_spmv.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int]
 lib.stmmqr_plan_solve_seminormal.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int,
                                              c_double_p]
+lib.stmmqr_plan_solve_minnorm.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int]
 lib.stmmqr_plan_solve_carried.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
 lib.stmmqr_plan_covariance_diag.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_int]
 lib.stmmqr_plan_leverage.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int]
@@ -577,6 +578,18 @@ class HipQR:
                "stmmqr_plan_solve_seminormal")
         return (X[:, 0] if np.ndim(B) == 1 else X), float(info.value)
 
+    def solve_minnorm(self, B: np.ndarray, permuted: bool = False) -> np.ndarray:
+        """With the plan holding the factorization of M (m x n): X = Q (R' \\ (E'B)) for B n or n x nrhs (permuted: B is already in
+        R's column order, X = Q (R' \\ B)), the minimum-2-norm solution of M(:, live)' x = b(live) in M's row order; dead columns have
+        no equation.  Both passes run on the device with nothing crossing to the host in between; qmult(1, rsolve(3, B)) bit for bit
+        where that route works, and no limit on the width of a front where it refuses.  Needs H."""
+        m, n = self.sym["m"], self.sym["n"]
+        Bf = np.array(B, dtype=np.float64, order="F", copy=True).reshape(n, -1, order="F")
+        X = np.zeros((m, Bf.shape[1]), order="F")
+        _check(lib.stmmqr_plan_solve_minnorm(self._h, Bf.ctypes.data, max(n, 1), X.ctypes.data, max(m, 1), Bf.shape[1], int(bool(permuted)), 0),
+               "stmmqr_plan_solve_minnorm")
+        return X[:, 0] if np.ndim(B) == 1 else X
+
     def solve_carried(self, nrhs: int):
         """Least squares with the right-hand sides carried through the factorization: the plan holds [A B] factorized with
         ntol = n (n = columns - nrhs, Qfill the identity on the B columns).  Returns (X, resid): X (n x nrhs) = E R11^-1 C with
@@ -869,6 +882,7 @@ lib.stmmqr_sparseqr_symbolic_view.argtypes = [C.c_void_p]
 lib.stmmqr_sparseqr_y.argtypes = [C.c_void_p, C.POINTER(c_long_p), C.POINTER(c_long_p), C.POINTER(c_double_p)]
 lib.stmmqr_sparseqr_qmult.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_long, C.c_long, C.c_long, c_double_p, C.c_long]
 lib.stmmqr_sparseqr_solve.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_long, C.c_long, c_double_p, C.c_long]
+lib.stmmqr_sparseqr_min2norm.argtypes = [C.c_void_p, c_double_p, C.c_long, C.c_long, c_double_p, C.c_long]
 
 
 lib.stmmqr_sparseqr_plan.restype = C.c_void_p
@@ -983,7 +997,7 @@ class SparseQR:
 
     @classmethod
     def lq(cls, m, n, Ap, Ai, Ax, tol=-2.0, relax: Relax | None = None, device=-1):
-        """SparseLQ (SparseLQ.c:691-734): the QR object of A' (L = R')."""
+        """SparseLQ (SparseLQ.c:691-734): the QR object of A' (L = R').  min2norm(b) on it is the minimum-2-norm solution of A x = b."""
         self = cls.__new__(cls)
         self._is_lq = True                                   # (the QR object of A': solve_seminormal would need A' as the matrix)
         self.m, self.n = int(n), int(m)
@@ -1015,6 +1029,17 @@ class SparseQR:
                                                     B.shape[1], _dp(X), self.n, int(refine), C.byref(info)),
                "stmmqr_sparseqr_solve_seminormal")
         return X, float(info.value)
+
+    def min2norm(self, B):
+        """On the QR object of A' (SparseQR.lq(A), or SparseQR of the transpose): the minimum-2-norm solution of A x = b,
+        x = Q (R' \\ (E'b)), for B self.n or self.n x nrhs -> self.m x nrhs.  The multifrontal part runs on the device in one call
+        (HipQR.solve_minnorm): unlike qmult(1, solve(3, B)) it has no limit on the width of a front.  Needs H."""
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim == 1:
+            B = B.reshape(-1, 1, order="F")
+        X = np.zeros((self.m, B.shape[1]), order="F")
+        _check(lib.stmmqr_sparseqr_min2norm(self._h, _dp(B), B.shape[0], B.shape[1], _dp(X), max(self.m, 1)), "stmmqr_sparseqr_min2norm")
+        return X
 
     def solve(self, system, B):
         B = np.asfortranarray(B, dtype=np.float64)

@@ -29,6 +29,8 @@ struct FrontSym {
     int nsched;              // panels of this front that get a step of the timeline (<= npanels: stmmqr_schedule.cpp, "how many panels")
     int qbig;                // Q-apply on the resident factors: the rows of this front are split over workgroups, one launch
                              // per panel (k_qbig_*), instead of one workgroup for the whole front (plan time)
+    int rtbig;               // R' x = b in the pass that takes fronts of any width (stmmqr_plan_solve_minnorm): the columns of this front
+                             // are split over workgroups (k_rtbig_*) -- k_rtsolve cannot hold it in LDS, or STMMQR_RTBIG_MIN (plan time)
 };
 
 // one pending block reflector (written by the panel kernel, read by the update kernel)
@@ -164,6 +166,15 @@ static inline long stm_lds_rtsolve(long fp, long fm_ub, long fn)
     const long fm1 = fm_ub > 1 ? fm_ub : 1;
     return (((fn + 1) & ~1L) + (((fp < fm1 ? fp : fm1) + 2) & ~1L)) * 8 + fp * 4 + 32;
 }
+
+// split R' solve (k_rtbig_*): one entry per split front of a tree level.  A workgroup of k_rtbig_step owns STM_RTB_COLS of the
+// front's columns, counted as its live pivot columns followed by its non-pivotal ones
+#define STM_RTB_NT 256
+#define STM_RTB_COLS 128
+struct RtDesc {
+    int f;                   // front
+    int lcoff;               // offset of its live-column list in the level's list (ints)
+};
 
 #define STM_QB_ROWS 512      // rows of a front per workgroup of the split Q-apply (k_qbig_step)
 // split Q-apply (k_qbig_*): one entry per large front of a tree level

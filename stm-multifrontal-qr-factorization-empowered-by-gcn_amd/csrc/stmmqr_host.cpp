@@ -186,6 +186,10 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
             // columns) or a short wide one whose columns are all pivotal (10 921 of them) -- the split kernels have no such limit
             const bool over_lds = stm_lds_qapply(fm, fn) > STM_RES_LDS_MAX || stm_lds_rsolve(fp, fn) > STM_RES_LDS_MAX;
             s.qbig = ((fm * fn >= qbig_min || over_lds) && fn >= 1) ? 1 : 0;
+            // R' x = b: the one-workgroup kernel keeps the front's u and x in LDS (6 550 columns of a square-ish front, 10 890 of a
+            // short wide one); a front beyond that is split over its columns (k_rtbig_*) by the pass that knows how, rt_pass_any.
+            // STMMQR_RTBIG_MIN splits smaller ones too
+            s.rtbig = (stm_lds_rtsolve(fp, fm, fn) > STM_RES_LDS_MAX || fm * fn >= knobs::num(knobs::K_RTBIG_MIN)) ? 1 : 0;
         }
         s.parent = (int)parent[f];
         s.foff = 0; s.coff = 0;                                    // (stm_assign_arenas, once the groups are known)

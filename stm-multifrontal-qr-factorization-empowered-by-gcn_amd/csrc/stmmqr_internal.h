@@ -28,6 +28,9 @@ int stm_sparseqr_order(int ordering, double tol, stm_long m, stm_long n, const s
                        const stm_long *Quser, stm_long *Q);
 // m, n of a factorized SparseQR object (stmmqr_sparseqr.cpp)
 int stm_sparseqr_dims(const stmmqr_qr *qr, stm_long *m, stm_long *n);
+// stmmqr_sparseqr_min2norm with the plan's solve handed in (stmmqr_plan_solve_minnorm): the singleton stages around it (stmmqr_sparseqr.cpp)
+typedef int (*stm_minnorm_fn)(stmmqr_plan *, const double *, stm_long, double *, stm_long, stm_long, int, int);
+int stm_sparseqr_min2norm(stmmqr_qr *qr, const double *B, stm_long ldb, stm_long nrhs, double *X, stm_long ldx, stm_minnorm_fn solve);
 }
 
 // Row form of a sparse matrix from its nz entries in storage order (row[p], col[p]): rp [m + 1], and row by row the entries' columns

@@ -158,8 +158,11 @@ int stm_launch_rsolve_big(const DevCtx &c, const QbDesc *qd, int nq, int max_ste
                           double *X, double *Acc, int *Lc, int *Rm, int *err, hipStream_t st, int nb, const RhsBatch &B);
 int stm_launch_rsolve(const DevCtx &c, const int *flist, int nfr, const int *Rj, const double *W, double *X, int lds_bytes,
                       int *err, hipStream_t st, int nb, const RhsBatch &B);
+// (skip_rtbig: the fronts with FrontSym::rtbig are left to stm_launch_rtsolve_big -- the pass that splits them; 0: every front)
 int stm_launch_rtsolve(const DevCtx &c, const int *flist, int nfr, const double *Bp, double *U, double *Xr, const int *rowbase,
-                       int lds_bytes, hipStream_t st, int nb, const RhsBatch &B);
+                       int lds_bytes, hipStream_t st, int nb, const RhsBatch &B, int skip_rtbig = 0);
+int stm_launch_rtsolve_big(const DevCtx &c, const RtDesc *rd, int nq, int max_steps, int max_nslab, const double *Bp, double *U, double *Xr,
+                           const int *rowbase, int *Lc, int *Rm, int *err, hipStream_t st, int nb, const RhsBatch &B);
 int stm_launch_panel_msg(void *const homes[6], const long long offs[6], const long long bytes[6], void *buf, int out, hipStream_t st);
 // subtree exchange: contribution blocks between plans as fixed-size messages, packed / unpacked on the device (stmmqr_pack.hip)
 struct StmFrontMsg { long long off, slot; int f, pad; };      // front f at buf + off: [8 | slot | fn - fp] doubles

@@ -40,7 +40,8 @@ enum When { PROCESS, PLAN, SCHED, RUN, CALL };
     X(RHS_BATCH, rhs_batch, int, INT, MIN1, PROCESS, 32, "right-hand sides per pass of the resident-factor operations (1: one vector after the other)")
 #define STM_KNOBS_PLAN(X)                                                                                                           \
     X(RH_EST_SCALE, rh_est_scale, double, REAL, PLAIN, PLAN, 1.0, "factor on the estimate that sizes the R+H arena (tests shrink it to drive the overflow path); every rebuild of the schedule keeps it") \
-    X(QBIG_MIN, qbig_min, long, INT, PLAIN, PLAN, 1L << 20, "entries of a front from which Q-apply / back substitution split its rows over workgroups")
+    X(QBIG_MIN, qbig_min, long, INT, PLAIN, PLAN, 1L << 20, "entries of a front from which Q-apply / back substitution split its rows over workgroups") \
+    X(RTBIG_MIN, rtbig_min, long, INT, PLAIN, PLAN, 1L << 62, "entries of a front from which the R' pass of the minimum-norm solve splits its columns over workgroups; by default only the fronts that one workgroup cannot hold (whether fronts that fit are faster split is unmeasured: the knob is there to tune that, and 1 lets tests send every front through the split kernels)")
 #define STM_KNOBS_SCHED(X)                                                                                                          \
     X(TUNE, tune, int, INT, PLAIN, SCHED, 0, "measurement sweeps of the update kernels (also read by every qr_front call)")         \
     X(CA_MIN, ca_min, int, INT, PLAIN, SCHED, 4096, "rows from which panel_algo 0 takes the Gram-based panel (= STM_CA_MIN_ROWS)")  \

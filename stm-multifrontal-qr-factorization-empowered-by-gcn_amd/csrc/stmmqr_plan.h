@@ -244,6 +244,15 @@ struct stmmqr_plan {
     DevBuf<double> d_W, d_Xs, d_Io, d_Xf, d_Wq, d_Xall, d_Yall, d_U, d_Xr;
     DevBuf<int> d_rowbase;                          // rows of R above each front (R rows are numbered front by front)
     std::vector<int> level_lds_rt;                  // dynamic LDS of k_rtsolve per level
+    // the R' pass that takes fronts of any width (rt_pass_any): per level, the fronts with FrontSym::rtbig (descriptors in d_rtb
+    // from off), their most blocks of 32 pivot columns and column slabs (plan time) / blocks of the factorization held, and the
+    // dynamic LDS k_rtsolve needs for the other fronts of the level
+    struct RtLevel { int off = 0, n = 0, max_steps = 0, max_nslab = 0, live_steps = 0, lds_small = 0; };
+    std::vector<RtLevel> level_rtbig;
+    std::vector<RtDesc> h_rtb;
+    DevBuf<RtDesc> d_rtb;
+    DevBuf<int> d_rtLc, d_rtRm;                     // live pivot columns of the level's split fronts (rtlc_ints) / their counts
+    long long rtlc_ints = 1;
     DevBuf<int> d_Dq;
     DevBuf<QbDesc> d_qb;
     // grouped split Q-apply (k_qbig_step4): T4 of every group of four panels of every split front, built at the first Q-apply after a

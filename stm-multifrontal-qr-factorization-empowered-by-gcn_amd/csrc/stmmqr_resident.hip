@@ -859,13 +859,14 @@ __global__ __launch_bounds__(RS_NT) void k_rsolve(DevCtx c, const int *__restric
 //   (rowbase[f] = rows of R above front f's).  Dead pivot columns have no equation (the squeezed R of the reference).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(RS_NT) void k_rtsolve(DevCtx c, const int *__restrict__ flist, const double *__restrict__ Bp,
-                                                   double *U, double *Xr, const int *__restrict__ rowbase, RhsBatch B)
+                                                   double *U, double *Xr, const int *__restrict__ rowbase, RhsBatch B, int skip_rtbig)
 {
     Bp += (long long)blockIdx.y * B.x; U += (long long)blockIdx.y * B.u; Xr += (long long)blockIdx.y * B.w;
     extern __shared__ double dyn_lds[];
     __shared__ int s_scan[RS_NT / 64];
     const int f = flist[blockIdx.x];
     const FrontSym s = c.fs[f];
+    if (skip_rtbig && s.rtbig) return;                  // (the pass that splits such fronts: k_rtbig_* below)
     const FrontNum nm = c.fnum[f];
     const int fp = s.fp, fn = s.fn, fm = nm.fm;
     const int tid = threadIdx.x;
@@ -946,6 +947,128 @@ __global__ __launch_bounds__(RS_NT) void k_rtsolve(DevCtx c, const int *__restri
         U[s.rp + k] = u[k] - ((a0 + a1) + (a2 + a3));
     }
     for (int r = tid; r < rm; r += RS_NT) Xr[rowbase[f] + r] = x[r];
+}
+
+// ------------------------------------------------------------------------------------------------
+// R' x = b for the fronts that k_rtsolve cannot hold (FrontSym::rtbig), the mirror of k_rbig_*: u stays in global memory, in the
+// front's own slots of the pass-vector array U[s.rp + 0 .. fn) (k_rtsolve only ever writes the slots k >= fp), and the columns are
+// split over workgroups.  init (one workgroup per front): live pivot columns -> Lc, rm; u = b on the pivotal columns, 0
+// elsewhere, plus the children's pass vectors.  Then one launch per block of 32 live pivot columns, first to last, right-looking:
+// every active workgroup solves the block's 32 x 32 lower triangle R' for itself (one wave, LDS; its right-hand sides u[lc[kb + j]]
+// are final, every earlier launch has completed) and subtracts R(kb : kb + nb, c)' x_blk from u[c] for the columns c of its own slab
+// that come after the block -- the later live pivot columns, then the non-pivotal ones (position v < rm: column lc[v], else column
+// fp + v - rm); workgroup 0 stores x.  A column has one writer per launch and nothing inside a launch waits for another
+// workgroup.  After the last block U[s.rp + k], k >= fp, is the pass vector.  Dead pivot columns have no equation: never read.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(RS_NT) void k_rtbig_init(DevCtx c, const RtDesc *__restrict__ rd, const double *__restrict__ Bp, double *U,
+                                                      int *Lc0, int *Rm, int *err, RhsBatch B)
+{
+    Bp += (long long)blockIdx.y * B.x; U += (long long)blockIdx.y * B.u;      // (Lc0 / Rm are the same for every right-hand side)
+    __shared__ int s_scan[RS_NT / 64];
+    const RtDesc d = rd[blockIdx.x];
+    const FrontSym s = c.fs[d.f];
+    const FrontNum nm = c.fnum[d.f];
+    const int fp = s.fp, fn = s.fn, fm = nm.fm, tid = threadIdx.x;
+    const int *St = c.Stair + s.rp;
+    int *lc = Lc0 + d.lcoff;
+    double *u = U + s.rp;
+    {
+        const int per = (fp + RS_NT - 1) / RS_NT;
+        const int k0 = min(fp, tid * per), k1 = min(fp, k0 + per);
+        int cnt = 0;
+        for (int k = k0; k < k1; k++) cnt += (St[k] != 0);
+        int total;
+        const int incl = qa_incl_scan<RS_NT / 64>(cnt, s_scan, &total);
+        int q = incl - cnt;
+        for (int k = k0; k < k1; k++) {
+            if (St[k] != 0 && q < fm) lc[q] = k;
+            q += (St[k] != 0);
+        }
+        if (tid == 0) {
+            const int rm = min(total, fm);
+            Rm[blockIdx.x] = rm;
+            if (rm != nm.rank) atomicExch(err, 1);          // (cannot happen: same rule as the factorization)
+        }
+    }
+    for (int k = tid; k < fn; k += RS_NT) u[k] = (k < fp) ? Bp[s.col1 + k] : 0.0;
+    __syncthreads();
+    for (int q = s.child0; q < s.child1; q++) {
+        const int ch = c.Child[q];
+        const FrontSym cs = c.fs[ch];
+        const int pc = cs.rp + cs.fp, cn = cs.fn - cs.fp;
+        for (int cj = tid; cj < cn; cj += RS_NT) u[c.Rjrel[pc + cj]] += U[pc + cj];     // (distinct targets within a child)
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(STM_RTB_NT) void k_rtbig_step(DevCtx c, const RtDesc *__restrict__ rd, int kstep, double *U, double *Xr,
+                                                           const int *__restrict__ rowbase, const int *Lc0, const int *Rm, RhsBatch B)
+{
+    U += (long long)blockIdx.z * B.u; Xr += (long long)blockIdx.z * B.w;
+    constexpr int QS_NB = 32;
+    __shared__ double s_tri[QS_NB][QS_NB + 1];
+    __shared__ double s_x[QS_NB];
+    const RtDesc d = rd[blockIdx.x];
+    const int rm = Rm[blockIdx.x];
+    const int kb = kstep * QS_NB;
+    if (kb >= rm) return;                                  // (a front with fewer blocks)
+    const int nb = min(QS_NB, rm - kb);
+    const FrontSym s = c.fs[d.f];
+    const int sl = blockIdx.y, tid = threadIdx.x;
+    const int v0 = max(sl * STM_RTB_COLS, kb + nb), v1 = min((sl + 1) * STM_RTB_COLS, rm + s.fn - s.fp);
+    if (sl != 0 && v0 >= v1) return;                       // no column after the block (workgroup 0 always runs: it stores x)
+    const double *F = c.Farena + s.foff;
+    const long long ld = s.ld;
+    const int *lc = Lc0 + d.lcoff;
+    double *u = U + s.rp;
+    // a half-wave per column, lanes along the block's rows (256 contiguous bytes of a column); half-wave g owns the positions
+    // g, g + NG, ... of the slab.  Its entries of R and its u are requested before the triangle is solved, as in k_rbig_step
+    const int lane32 = tid & 31, grp = tid >> 5;
+    constexpr int NG = STM_RTB_NT / 32, NC = STM_RTB_COLS / NG;
+    const int nv = rm + s.fn - s.fp;
+    const double *Fr = F + kb + lane32;
+    double fv[NC];
+#pragma unroll
+    for (int q = 0; q < NC; q++) {
+        const int v = sl * STM_RTB_COLS + grp + NG * q;
+        const int col = (v >= kb + nb && v < nv) ? ((v < rm) ? lc[v] : s.fp + (v - rm)) : -1;
+        fv[q] = (col >= 0 && lane32 < nb) ? Fr[(long long)col * ld] : 0.0;
+    }
+    int mycol = -1;                                        // lane q < NC stores the half-wave's column q
+    {
+        const int v = sl * STM_RTB_COLS + grp + NG * lane32;
+        if (lane32 < NC && v >= kb + nb && v < nv) mycol = (v < rm) ? lc[v] : s.fp + (v - rm);
+    }
+    const double myu = (mycol >= 0) ? u[mycol] : 0.0;      // (written by this half-wave alone in this launch)
+    const double rhs = (tid < nb) ? u[lc[kb + tid]] : 0.0;  // the block's own right-hand sides: no launch after the previous one writes them
+    for (int e = tid; e < QS_NB * QS_NB; e += STM_RTB_NT) {
+        const int i = e % QS_NB, j = e / QS_NB;            // R(kb + i, column j of the block), i <= j
+        s_tri[i][j] = (i < nb && j < nb && i <= j) ? F[(kb + i) + (long long)lc[kb + j] * ld] : 0.0;
+    }
+    __syncthreads();
+    if (tid < 64) {
+        // lane j owns equation j: x_j = (u_j - sum_{i<j} R(i,j) x_i) / R(j,j)
+        const int j = tid;
+        double a = rhs;
+        for (int i = 0; i < nb; i++) {
+            const double ai = __shfl(a, i, 64);
+            const double xi = ai / s_tri[i][i];
+            if (j > i && j < nb) a -= s_tri[i][j] * xi;
+            if (j == i) s_x[i] = xi;
+        }
+        if (j >= nb && j < QS_NB) s_x[j] = 0.0;
+    }
+    __syncthreads();
+    if (sl == 0 && tid < nb) Xr[rowbase[d.f] + kb + tid] = s_x[tid];
+    const double xi = s_x[lane32];
+    double mine = 0.0;
+#pragma unroll
+    for (int q = 0; q < NC; q++) {
+        double p = fv[q] * xi;
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+        if (lane32 == q) mine = p;
+    }
+    if (mycol >= 0) u[mycol] = myu - mine;
 }
 
 // scatter: out[perm[i]] = in[i]   gather: out[i] = in[perm[i]]   (perm == nullptr: identity)
@@ -1196,10 +1319,20 @@ int stm_launch_rsolve_big(const DevCtx &c, const QbDesc *qd, int nq, int max_ste
     return (int)hipGetLastError();
 }
 int stm_launch_rtsolve(const DevCtx &c, const int *flist, int nfr, const double *Bp, double *U, double *Xr, const int *rowbase,
-                       int lds_bytes, hipStream_t st, int nb, const RhsBatch &B)
+                       int lds_bytes, hipStream_t st, int nb, const RhsBatch &B, int skip_rtbig)
 {
     if (nfr <= 0) return 0;
-    hipLaunchKernelGGL(k_rtsolve, dim3(nfr, nb), dim3(RS_NT), (size_t)lds_bytes, st, c, flist, Bp, U, Xr, rowbase, B);
+    hipLaunchKernelGGL(k_rtsolve, dim3(nfr, nb), dim3(RS_NT), (size_t)lds_bytes, st, c, flist, Bp, U, Xr, rowbase, B, skip_rtbig);
+    return (int)hipGetLastError();
+}
+// forward substitution of the split fronts of one level: init, then a launch per block of 32 live pivot columns
+int stm_launch_rtsolve_big(const DevCtx &c, const RtDesc *rd, int nq, int max_steps, int max_nslab, const double *Bp, double *U, double *Xr,
+                           const int *rowbase, int *Lc, int *Rm, int *err, hipStream_t st, int nb, const RhsBatch &B)
+{
+    if (nq <= 0) return 0;
+    hipLaunchKernelGGL(k_rtbig_init, dim3(nq, nb), dim3(RS_NT), 0, st, c, rd, Bp, U, Lc, Rm, err, B);
+    for (int k = 0; k < max_steps; k++)
+        hipLaunchKernelGGL(k_rtbig_step, dim3(nq, max_nslab, nb), dim3(STM_RTB_NT), 0, st, c, rd, k, U, Xr, rowbase, (const int *)Lc, (const int *)Rm, B);
     return (int)hipGetLastError();
 }
 int stm_launch_perm(const double *in, const int *perm, double *out, int n, int scatter, hipStream_t st, int nb, long long sin, long long sout)

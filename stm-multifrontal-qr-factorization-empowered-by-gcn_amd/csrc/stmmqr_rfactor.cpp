@@ -153,13 +153,16 @@ int build_resident_tables(stmmqr_plan &P)
     P.level_lds_rs.assign(LV.size(), 0);
     P.level_lds_rt.assign(LV.size(), 0);
     P.level_qbig.assign(LV.size(), stmmqr_plan::QbLevel());
+    P.level_rtbig.assign(LV.size(), stmmqr_plan::RtLevel());
+    P.h_rtb.clear(); P.rtlc_ints = 1;
     P.t4items.clear(); P.t4fronts.clear(); P.t4dqo.clear(); P.qbt4off.clear();
     P.t4_doubles = 0; P.dq4_ints = 0; P.t4_ok = false; P.t4_tried = false; P.t4_valid = false;
     std::vector<QbDesc> qb;
     long xf = 1, dq = 1, wq = 1;
     for (size_t l = 0; l < LV.size(); l++) {
-        long xo = 0, dqo = 0, wo = 0;
+        long xo = 0, dqo = 0, wo = 0, lco = 0;
         P.level_qbig[l].off = (int)qb.size();
+        P.level_rtbig[l].off = (int)P.h_rtb.size();
         P.level_qbig[l].t4i_off = (int)P.t4items.size();
         for (int q = 0; q < LV[l].n_all; q++) {
             const int f = P.lists[LV[l].all_off + q];
@@ -167,6 +170,18 @@ int build_resident_tables(stmmqr_plan &P)
             const int need = (int)std::min(stm_lds_qapply(s.fm_ub, s.fn), (long)INT_MAX);
             P.level_lds_rt[l] = std::max(P.level_lds_rt[l], (int)std::min(stm_lds_rtsolve(s.fp, s.fm_ub, s.fn), (long)INT_MAX));
             P.level_lds_qa_all[l] = std::max(P.level_lds_qa_all[l], need);
+            if (s.rtbig) {
+                auto &T = P.level_rtbig[l];
+                RtDesc d;
+                d.f = f; d.lcoff = (int)lco;
+                P.h_rtb.push_back(d);
+                lco += s.fp;
+                const int rmax = std::min(s.fp, s.fm_ub);
+                T.n++; T.max_steps = std::max(T.max_steps, (rmax + 31) / 32);
+                T.max_nslab = std::max(T.max_nslab, std::max(1, (rmax + s.fn - s.fp + STM_RTB_COLS - 1) / STM_RTB_COLS));
+            } else {
+                P.level_rtbig[l].lds_small = std::max(P.level_rtbig[l].lds_small, (int)stm_lds_rtsolve(s.fp, s.fm_ub, s.fn));
+            }
             if (s.qbig) {
                 QbDesc d;
                 d.f = f; d.xoff = (int)xo; d.dqoff = (int)dqo; d.wqoff = (int)wo; d.nslab = (s.fm_ub + STM_QB_ROWS - 1) / STM_QB_ROWS; d.np_live = s.npanels;
@@ -194,13 +209,15 @@ int build_resident_tables(stmmqr_plan &P)
         }
         P.level_qbig[l].t4i_n = (int)P.t4items.size() - P.level_qbig[l].t4i_off;
         xf = std::max(xf, xo); dq = std::max(dq, dqo); wq = std::max(wq, wo);
+        P.rtlc_ints = std::max(P.rtlc_ints, (long long)lco);
     }
     LCHK(P.d_Xf.alloc((size_t)xf));
     LCHK(P.d_Dq.alloc((size_t)dq));
     LCHK(P.d_Wq.alloc((size_t)wq));
     P.wq4_doubles = 4 * wq;
     P.xf_doubles = xf; P.wq_doubles = wq; P.rhs_cap = 1;
-    P.d_U.release(); P.d_Xr.release();
+    P.d_U.release(); P.d_Xr.release(); P.d_rtLc.release(); P.d_rtRm.release();
+    if (!P.h_rtb.empty()) LCHK(P.d_rtb.upload(P.h_rtb, st));
     if (qb.empty()) qb.push_back(QbDesc());
     LCHK(P.d_qb.alloc(qb.size()));
     LCHK(P.d_Rm.alloc(qb.size()));
@@ -234,6 +251,11 @@ int count_live_panels(stmmqr_plan &P)
             Q.live_np = std::max(Q.live_np, npl);
             Q.live_rsteps = std::max(Q.live_rsteps, live ? (int)((nm.rank + 31) / 32) : Q.max_rsteps);
         }
+    }
+    for (size_t l = 0; l < P.level_rtbig.size(); l++) {
+        auto &T = P.level_rtbig[l];
+        T.live_steps = live ? 0 : T.max_steps;
+        for (int q = 0; q < T.n && live; q++) T.live_steps = std::max(T.live_steps, (int)((P.h_fnum[P.h_rtb[(size_t)(T.off + q)].f].rank + 31) / 32));
     }
     if (changed && !P.h_qb.empty()) HIPCHK(hipMemcpy(P.d_qb.p, P.h_qb.data(), P.h_qb.size() * sizeof(QbDesc), hipMemcpyHostToDevice));
     return 0;
@@ -440,15 +462,19 @@ int r_vectors(stmmqr_plan &P, const double *Y, double *X, int nb, bool through_q
 // The forward pass, R' x = b, from the leaves to the root: b in R's column order in d_Xs (nb vectors at stride n) -> d_Xr (R's row
 // order, stride m; rows beyond the rank stay zero).  ensure_rt comes before the first batch: it refuses a tree that k_rtsolve cannot
 // take and makes the pass's own buffers (U, Xr) at the plan's current batch size, from where ensure_rhs_batch grows them.
-int ensure_rt(stmmqr_plan &P)
+int ensure_rt_buffers(stmmqr_plan &P)
 {
-    for (int need : P.level_lds_rt)
-        if (need > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front is too wide for the one-workgroup R' solve");
     if (!P.d_U.p) {
         LCHK(P.d_U.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, P.rjsize)));
         LCHK(P.d_Xr.alloc((size_t)P.rhs_cap * (size_t)std::max(1L, P.m)));
     }
     return 0;
+}
+int ensure_rt(stmmqr_plan &P)
+{
+    for (int need : P.level_lds_rt)
+        if (need > STM_RES_LDS_MAX) return fail(STMMQR_ERR_TOO_LARGE, "a front is too wide for the one-workgroup R' solve");
+    return ensure_rt_buffers(P);
 }
 int rt_pass(stmmqr_plan &P, int nb)
 {
@@ -460,6 +486,37 @@ int rt_pass(stmmqr_plan &P, int nb)
     for (size_t l = 0; l < LV.size(); l++) {
         LCHK(level_to_front_form(P, l));
         LCHK(stm_launch_rtsolve(c, L0 + LV[l].all_off, LV[l].n_all, P.d_Xs.p, P.d_U.p, P.d_Xr.p, P.d_rowbase.p, P.level_lds_rt[l], P.stream, nb, B));
+    }
+    return 0;
+}
+// The same pass for a tree with fronts of any width: the fronts with FrontSym::rtbig go through k_rtbig_* (init + a launch per
+// block of 32 live pivot columns, all split fronts of a level together), the others through k_rtsolve as above; the fronts of a level
+// are independent.  A split front leaves its pass vector where k_rtsolve leaves it, so either kind feeds either kind.  Sets d_err
+// on an inconsistent front (end_resident_op).  ensure_rt_any comes before the first batch; it refuses nothing.
+int ensure_rt_any(stmmqr_plan &P)
+{
+    LCHK(ensure_rt_buffers(P));
+    if (!P.d_rtLc.p && !P.h_rtb.empty()) {
+        LCHK(P.d_rtLc.alloc((size_t)P.rtlc_ints));
+        LCHK(P.d_rtRm.alloc(P.h_rtb.size()));
+    }
+    return 0;
+}
+int rt_pass_any(stmmqr_plan &P, int nb)
+{
+    const RhsBatch B = rhs_strides(P);
+    DevCtx c = res_ctx(P);
+    const int *L0 = P.d_lists.p;
+    const auto &LV = P.glevels[0];
+    HIPCHK(hipMemsetAsync(P.d_Xr.p, 0, (size_t)nb * (size_t)std::max(1L, P.m) * sizeof(double), P.stream));
+    for (size_t l = 0; l < LV.size(); l++) {
+        const auto &T = P.level_rtbig[l];
+        if (T.lds_small > STM_RES_LDS_MAX) return fail(STMMQR_ERR_INVALID, "internal: a front that k_rtsolve cannot hold was not split");
+        LCHK(level_to_front_form(P, l));
+        if (T.n < LV[l].n_all)
+            LCHK(stm_launch_rtsolve(c, L0 + LV[l].all_off, LV[l].n_all, P.d_Xs.p, P.d_U.p, P.d_Xr.p, P.d_rowbase.p, T.lds_small, P.stream, nb, B, 1));
+        LCHK(stm_launch_rtsolve_big(c, P.d_rtb.p + T.off, T.n, T.live_steps, T.max_nslab, P.d_Xs.p, P.d_U.p, P.d_Xr.p, P.d_rowbase.p, P.d_rtLc.p,
+                                    P.d_rtRm.p + T.off, P.d_err.p, P.stream, nb, B));
     }
     return 0;
 }
@@ -559,6 +616,36 @@ int stmmqr_plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *
         return 0;
     }));
     LCHK(download_cols(P, P.d_Yall, X, ldx, n, nrhs));
+    return end_resident_op(P);
+}
+
+// The minimum-2-norm solution of an underdetermined system from the factorization of its transpose: X = Q (R' \ (E' B)), all on the
+// device -- the R' pass that takes fronts of any width, then the Q pass fed from its result; see include/stmmqr_hip.h
+int stmmqr_plan_solve_minnorm(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int permuted,
+                              int on_device)
+{
+    PASS(check_factored(plan));
+    if (!B || !X || nrhs < 0) return fail(STMMQR_ERR_INVALID, "bad minimum-norm solve arguments");
+    if (ldb < plan->n || ldx < plan->m) return fail(STMMQR_ERR_INVALID, "bad leading dimension");
+    if (!plan->keep_h)
+        return fail(STMMQR_ERR_INVALID, "the plan keeps no Householder vectors (keepH = 0): no Q-apply, so no minimum-norm solve");
+    stmmqr_plan &P = *plan;
+    PASS(begin_resident_op(P));
+    hipStream_t st = P.stream;
+    const long m = P.m, n = P.n;
+    if (nrhs == 0 || m == 0) return 0;
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
+    LCHK(grow(P.d_Xall, (size_t)(std::max(1L, n) * nrhs)));
+    LCHK(grow(P.d_Yall, (size_t)(m * nrhs)));
+    PASS(copy_cols(P.d_Xall.p, n, B, ldb, n, nrhs, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    PASS(ensure_rt_any(P));
+    PASS(for_each_batch(P, nrhs, [&](stm_long j, int nb) -> int {
+        // b in R's column order (E'B gathers through Qfill), y = R' \ b in R's row order, x = Q y in the caller's row order
+        LCHK(stm_launch_perm(P.d_Xall.p + j * n, (!permuted && P.has_qfill) ? P.d_Qfill.p : nullptr, P.d_Xs.p, (int)n, 0, st, nb, n, n));
+        PASS(rt_pass_any(P, nb));
+        return qapply_vectors(P, 1, P.d_Xr.p, P.d_Yall.p + j * m, nb);
+    }));
+    LCHK(download_cols(P, P.d_Yall, X, ldx, m, nrhs, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return end_resident_op(P);
 }
 
@@ -990,6 +1077,13 @@ int stm_aop_apply(stm_aop *op, int trans, const double *X, stm_long ldx, const d
     PASS(copy_cols(Y, ldy, op->Y.p, yr, yr, nrhs, hipMemcpyDeviceToHost, op->st));
     HIPCHK(hipStreamSynchronize(op->st));
     return 0;
+}
+
+// The minimum-2-norm solution of A x = b on the QR object of A'; see include/stmmqr_hip.h.  The singleton stages are host code of the
+// object (stmmqr_sparseqr.cpp), the multifrontal part is stmmqr_plan_solve_minnorm
+int stmmqr_sparseqr_min2norm(stmmqr_qr *qr, const double *B, stm_long ldb, stm_long nrhs, double *X, stm_long ldx)
+{
+    return stm_sparseqr_min2norm(qr, B, ldb, nrhs, X, ldx, stmmqr_plan_solve_minnorm);
 }
 
 // Least squares by the corrected seminormal equations on a SparseQR object (with or without H): x = E R^-1 R^-T E' A'b, then

@@ -570,4 +570,44 @@ int stmmqr_sparseqr_solve(stmmqr_qr *qr, int system, const double *B, stm_long l
     }
 }
 
+// ---- minimum-2-norm solution of A x = b on the QR object of A': x = Q (R' \ (E' b)).  With singletons: the host stage through R1 as
+//      in system 3 above, the multifrontal part on the device in one call (no limit on a front's width), then the row scatter of
+//      QR_QX as in stmmqr_sparseqr_qmult.  This file is host code only (it is also built without the device half of the library),
+//      so the plan's solve comes in as `solve`: stmmqr_sparseqr_min2norm itself is in stmmqr_rfactor.cpp ----
+int stm_sparseqr_min2norm(stmmqr_qr *qr, const double *B, stm_long ldb, stm_long nrhs, double *X, stm_long ldx, stm_minnorm_fn solve)
+{
+    if (!qr || !B || !X || nrhs < 0) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_min2norm: bad arguments");
+    if (!qr->keep_h) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_min2norm: the factorization keeps no Householder vectors (keepH = 0)");
+    const Long m = qr->m, n = qr->n, n1r = qr->n1rows, n1c = qr->n1cols, n2 = n - n1c, m2 = m - n1r;
+    if (ldb < n || ldx < m) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_min2norm: bad leading dimension");
+    if (nrhs == 0) return 0;
+    try {
+        if (n1c == 0) return solve(qr->plan, B, ldb, X, ldx, nrhs, 0, 0);                       // (the plan's Qfill is Q1fill)
+        std::vector<double> b((size_t)n), x1((size_t)std::max<Long>(n1r, 1) * (size_t)nrhs), B2((size_t)std::max<Long>(n2, 1) * (size_t)nrhs),
+            Z((size_t)std::max<Long>(m2, 1) * (size_t)nrhs, 0.0);
+        for (Long j = 0; j < nrhs; j++) {
+            for (Long k = 0; k < n; k++) b[(size_t)k] = B[qr->Q1fill[(size_t)k] + j * ldb];  // b in R's column order
+            for (Long i = 0; i < n1r; i++) {
+                const Long p0 = qr->R1p[(size_t)i];
+                const double xi = b[(size_t)qr->R1j[(size_t)p0]] / qr->R1x[(size_t)p0];
+                x1[(size_t)i + (size_t)j * (size_t)n1r] = xi;
+                for (Long p = p0 + 1; p < qr->R1p[(size_t)i + 1]; p++) b[(size_t)qr->R1j[(size_t)p]] -= qr->R1x[(size_t)p] * xi;
+            }
+            for (Long k = 0; k < n2; k++) B2[(size_t)k + (size_t)j * (size_t)std::max<Long>(n2, 1)] = b[(size_t)(n1c + k)];
+        }
+        if (n2 > 0 && m2 > 0) {
+            const int e = solve(qr->plan, B2.data(), std::max<Long>(n2, 1), Z.data(), std::max<Long>(m2, 1), nrhs, 1, 0);
+            if (e) return e;
+        }
+        for (Long j = 0; j < nrhs; j++)
+            for (Long i = 0; i < m; i++) {
+                const Long k = qr->P1inv[(size_t)i];
+                X[i + j * ldx] = (k < n1r) ? x1[(size_t)k + (size_t)j * (size_t)n1r] : Z[(size_t)(k - n1r) + (size_t)j * (size_t)std::max<Long>(m2, 1)];
+            }
+        return 0;
+    } catch (const std::bad_alloc &) {
+        return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_sparseqr_min2norm: out of memory");
+    }
+}
+
 }  // extern "C"
