@@ -385,7 +385,8 @@ int stmmqr_plan_rsolve(stmmqr_plan *plan, int system, const double *B, stm_long 
  *                                with on_device).  Works on plans with and without H and reads R only.  Dead columns get x = 0
  *                                (the basic solution).  info (may be NULL): the largest |A'r| / (|A|_F (|A|_F |x| + |b|)) over the
  *                                right-hand sides, r = b - A x of the returned x.  Accurate to about cond(A) u only while
- *                                cond(A)^2 u << 1: above cond(A) ~ 1e7 the Q-based stmmqr_plan_solve is the right tool.  A front too
+ *                                cond(A)^2 u << 1: above cond(A) ~ 1e7 the Q-based stmmqr_plan_solve is the right tool
+ *                                (stmmqr_plan_condest below estimates cond(A) from the factors the plan holds).  A front too
  *                                wide for the one-workgroup R' solve gives STMMQR_ERR_TOO_LARGE, as stmmqr_plan_rsolve systems 2-3.
  *                                (stmmqr_plan_solve_minnorm below has no such limit: its R' pass splits such fronts.) */
 int stmmqr_plan_keep_h(const stmmqr_plan *plan);
@@ -405,6 +406,55 @@ int stmmqr_plan_solve_seminormal(stmmqr_plan *plan, const double *B, stm_long ld
  * keepH, as stmmqr_plan_qmult's).  nrhs = 0 returns 0 and writes nothing. */
 int stmmqr_plan_solve_minnorm(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs,
                               int permuted, int on_device);
+
+/* Products with R itself on the resident factors.  R is the whole rank x n factor, dead pivot columns included (they keep the rows
+ * above them): the matrix of A E = Q R, so stmmqr_plan_qmult(1, .) of the result of trans = 0 reproduces A x.
+ *   trans = 0: X is n x nrhs (ldx >= n), Y is m x nrhs (ldy >= m) in R's row order -- what stmmqr_plan_qmult method 0 returns and
+ *              method 1 takes.  Y = R X (permuted != 0: X is in R's column order) or R (E' X) (permuted == 0: X is in the caller's
+ *              column order and is gathered through Qfill).  Rows beyond the rank are written as zero.
+ *   trans = 1: X is m x nrhs, rows beyond the rank are not read; Y is n x nrhs.  Y = R' X or E (R' X).
+ * Reads R only: plans with and without H, and no limit on the width or height of a front.  on_device: X and Y are device pointers.
+ * Deterministic: every entry is summed in an order fixed by the front it belongs to -- no atomics (R' X adds every front's column
+ * dots in the order of the fronts) -- so column j of a batch carries the bits of the one-vector call, host and device output carry
+ * the same bits, and so do plans with and without H.  Batches of STMMQR_RHS_BATCH vectors share one pass.  trans = 0 allocates
+ * nothing beyond the caller's vectors; the index and the slot array the transposed product needs (the transpose of Rj, one double
+ * per entry of Rj and vector of a batch) are made at the first call with trans = 1; a plan that never calls this allocates nothing for it.
+ * Refusals (STMMQR_ERR_INVALID, the plan stays usable): nothing factorized, trans not 0 or 1, bad pointers or leading dimensions.
+ * nrhs = 0 returns 0 and writes nothing. */
+int stmmqr_plan_rmult(stmmqr_plan *plan, int trans, const double *X, stm_long ldx, double *Y, stm_long ldy, stm_long nrhs, int permuted,
+                      int on_device);
+
+/* The condition number of the held factorization, estimated on the device.  R_live = R over its live pivot columns (rank x rank, upper
+ * triangular); since A E = Q R, cond(R_live) = cond(A(:, live)) in the 2-norm, and within a factor sqrt(m) of it in the 1-norm.
+ *   kind = 1: the one-norm, the convention of LAPACK's dtrcon / dlacn2.  |R_live|_1 is exact (column sums on the device);
+ *             |R_live^-1|_1 is Hager's estimate in Higham's form: from x = 1/r at most five rounds of y = R \ x, xi = sign(y),
+ *             z = R' \ xi, x = e_j at the first largest |z_j|, until |z|_inf <= z'x, the arg-max repeats or the estimate stops
+ *             growing; then the safeguard vector x_i = (-1)^i (1 + i / (r - 1)) with estimate 2 |R \ x|_1 / (3 r); the larger of
+ *             the two.  Cost: out[3] rounds, each a solve with R and one with R', plus one solve with R (typically 2-3 rounds).
+ *   kind = 2: the two-norm.  `iters` steps (iters <= 0: 8) of the power iteration on R'R for |R_live|_2 and of the same iteration
+ *             on its inverse (a solve with R' and one with R per step) for |R_live^-1|_2 = 1 / |R_live v|_2 of its last iterate v;
+ *             both start from the safeguard vector, normalised.  Cost: iters solve pairs and 2 iters + 1 products with R.
+ * Both kinds are LOWER bounds of the condition number: every quantity is |M x| / |x| of some x.  Expect 0.7 .. 1 of the true
+ * one-norm condition, and 0.9 .. 1 of the two-norm condition after 8 steps (measured: DESIGN.md 6k).  All vectors stay on the
+ * device; the host reads a few scalars per round.
+ *   out[0] the condition estimate = out[1] * out[2]     out[1] the norm of R_live     out[2] the estimated norm of its inverse
+ *   out[3] kind 1: the rounds entered -- every round is a solve with R, and every round but possibly the last (the one that stops
+ *          because the estimate did not grow, or the fifth) a solve with R' as well; the safeguard's one solve with R is not counted.
+ *          kind 2: the solve pairs of the inverse iteration whose result became the iterate (iters, unless a zero or non-finite
+ *          norm ended it early)
+ *   out[4] r = the number of live pivot columns     out[5] kind     out[6..7] 0
+ *   r = 0: condition 1, norms 0, nothing is launched.
+ *   v non-NULL [ncol]: an approximate null vector in the caller's column order, zero on dead columns, of unit norm of the kind.
+ *   kind 1: R_live^-1 x / |R_live^-1 x|_1 of the x that attained the estimate, so |R_live v|_1 = 1 / out[2] (MATLAB's
+ *   [c, v] = condest(A)); kind 2: the last iterate of the inverse iteration, |R_live v|_2 = 1 / out[2].  It lets a caller verify
+ *   the estimate without trusting the iteration.
+ *   ncol < the columns of the plan: the plan holds [A B] as stmmqr_plan_solve_carried expects it (the same messages) and the
+ *   trailing columns take no part.  on_device: out and v are device pointers.
+ * Reads R only: plans with and without H, fronts of any width (the R' solves are those of stmmqr_plan_solve_minnorm).  Its vectors
+ * are made at the first call.  STMMQR_ERR_INVALID (the message says why; the plan stays usable): null plan or nothing factorized, out
+ * NULL, ncol out of range, kind not 1 or 2, the carried conditions not met for ncol < n, or a plan that does not hold the whole tree. */
+int stmmqr_plan_condest(stmmqr_plan *plan, stm_long ncol, int kind, int iters, double *out /* [8] */, double *v /* [ncol] or NULL */,
+                        int on_device);
 
 /* Least squares with the right-hand sides carried through the factorization: the plan holds a factorization of the m x (n + nrhs)
  * matrix [A B] made with ntol = n (the columns of B are never rank-tested), whose Qfill is the identity on the last nrhs columns.
@@ -437,7 +487,8 @@ int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_l
  * Accuracy: the recurrence forms entries of (R'R)^-1, whose condition is cond(A)^2, so an entry carries an error of about
  * u cond(A)^2 times the largest one -- as the normal equations would.  Up to cond(A) ~ 1e7 every variance has digits to spare
  * (measured: DESIGN.md 6h); on lns_3937 (cond ~ 1e11) 45 of 1822 variances are off by more than 1e-3 relative and four are negative.
- * There |stmmqr_plan_rsolve(system 3, e_j)|^2 gives column j to u cond(A), one column at a time.
+ * There |stmmqr_plan_rsolve(system 3, e_j)|^2 gives column j to u cond(A), one column at a time.  stmmqr_plan_condest below tells
+ * which side of that threshold the held factorization is on.
  * Entries off the diagonal and the leverages of the rows come from the same blocks: stmmqr_plan_covariance_entries and
  * stmmqr_plan_leverage below.  Out of scope: entries outside the pattern of the selected inverse, and a stmmqr_sparseqr_* entry (the
  * singleton block R1 lives on the host and is no part of the plan; the stmmqr_ls object removes no singletons and is the home of
@@ -667,6 +718,9 @@ int stmmqr_ls_covariance_diag(stmmqr_ls *ls, double *var, int on_device);   /* a
  * They refuse as stmmqr_ls_covariance_diag does: null object, the host half only, no solve yet. */
 int stmmqr_ls_leverage(stmmqr_ls *ls, double *lev, double *var, int on_device);
 int stmmqr_ls_covariance_entries(stmmqr_ls *ls, stm_long npairs, const stm_long *I, const stm_long *J, double *out, int on_device);
+/* after a solve: stmmqr_plan_condest with ncol = n of A -- the condition of A(:, live), which says how far the solution, the variances
+ * and the leverages above can be trusted (out [8], v [n] or NULL).  Refuses as stmmqr_ls_covariance_diag does. */
+int stmmqr_ls_condest(stmmqr_ls *ls, int kind, int iters, double *out, double *v, int on_device);
 void stmmqr_ls_free(stmmqr_ls *ls);
 
 void stmmqr_shutdown(void);                           /* optional end-of-use call for dlopen()ing hosts: device sync  */

@@ -153,6 +153,8 @@ lib.stmmqr_plan_solve_seminormal.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C
 lib.stmmqr_plan_solve_minnorm.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int]
 lib.stmmqr_plan_solve_carried.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
 lib.stmmqr_plan_covariance_diag.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_int]
+lib.stmmqr_plan_rmult.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int]
+lib.stmmqr_plan_condest.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_plan_leverage.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_plan_covariance_entries.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_set_keep_h.argtypes = [C.c_void_p, C.c_int]
@@ -308,6 +310,17 @@ class QRNumeric:
         self.rh_total = rh_total
         self.rank = self.rank1 = self.maxfrank = self.maxfm = 0
         self.stats = {}
+
+
+def _condest_dict(call, what, ncol, with_vector):
+    """call(out, v) of a condest entry point with host arrays -> the dict HipQR.condest / LeastSquares.condest return"""
+    out = np.zeros(8)
+    v = np.zeros(max(ncol, 1)) if with_vector else None
+    _check(call(out.ctypes.data, None if v is None else v.ctypes.data), what)
+    d = {"cond": float(out[0]), "norm": float(out[1]), "inv_norm": float(out[2]), "rounds": int(out[3]), "r": int(out[4]), "kind": int(out[5])}
+    if with_vector:
+        d["v"] = v[:max(ncol, 0)]
+    return d
 
 
 class HipQR:
@@ -589,6 +602,29 @@ class HipQR:
         _check(lib.stmmqr_plan_solve_minnorm(self._h, Bf.ctypes.data, max(n, 1), X.ctypes.data, max(m, 1), Bf.shape[1], int(bool(permuted)), 0),
                "stmmqr_plan_solve_minnorm")
         return X[:, 0] if np.ndim(B) == 1 else X
+
+    def rmult(self, X: np.ndarray, trans: int = 0, permuted: bool = False) -> np.ndarray:
+        """Products with the whole rank x n factor R on the device (stmmqr_plan_rmult), dead pivot columns included.  trans = 0: X is n
+        or n x nrhs, returns R (E'X) (permuted: X is in R's column order, R X) as m rows in R's row order -- what qmult(0, .) returns
+        and qmult(1, .) takes; rows beyond the rank are zero.  trans = 1: X has m rows (those beyond the rank are ignored), returns
+        E (R'X) or R'X.  Reads R only; column j of a batch carries the bits of the one-vector call."""
+        m, n = self.sym["m"], self.sym["n"]
+        xr, yr = (m, n) if trans else (n, m)
+        Xf = np.array(X, dtype=np.float64, order="F", copy=True).reshape(xr, -1, order="F")
+        Y = np.zeros((yr, Xf.shape[1]), order="F")
+        _check(lib.stmmqr_plan_rmult(self._h, int(trans), Xf.ctypes.data, max(xr, 1), Y.ctypes.data, max(yr, 1), Xf.shape[1],
+                                     int(bool(permuted)), 0), "stmmqr_plan_rmult")
+        return Y[:, 0] if np.ndim(X) == 1 else Y
+
+    def condest(self, kind: int = 1, iters: int = 0, ncol=None, with_vector: bool = False) -> dict:
+        """The condition of R over its live pivot columns -- of A(:, live) -- estimated on the device (stmmqr_plan_condest).  kind 1:
+        the one-norm, exact |R_live|_1 times Hager / Higham's estimate of |R_live^-1|_1 (LAPACK's dtrcon convention); kind 2: the
+        two-norm by `iters` (default 8) steps of the power iteration on R'R and on its inverse.  Both are lower bounds.  ncol as in
+        covariance_diag.  Returns {"cond", "norm", "inv_norm", "rounds", "r", "kind"} and, with_vector, "v": an approximate null
+        vector in the caller's column order with zeros on dead columns, unit norm of the kind and |R_live v| = 1 / inv_norm."""
+        return _condest_dict(lambda out, v: lib.stmmqr_plan_condest(self._h, self.sym["n"] if ncol is None else int(ncol), int(kind), int(iters),
+                                                                    out, v, 0),
+                             "stmmqr_plan_condest", self.sym["n"] if ncol is None else int(ncol), with_vector)
 
     def solve_carried(self, nrhs: int):
         """Least squares with the right-hand sides carried through the factorization: the plan holds [A B] factorized with
@@ -1063,6 +1099,7 @@ lib.stmmqr_ls_resid.argtypes = [C.c_void_p, c_double_p]
 lib.stmmqr_ls_covariance_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_ls_leverage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_ls_covariance_entries.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+lib.stmmqr_ls_condest.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_ls_free.restype = None
 lib.stmmqr_ls_free.argtypes = [C.c_void_p]
 
@@ -1154,6 +1191,11 @@ class LeastSquares:
         var = np.zeros(max(self.n, 1))
         _check(lib.stmmqr_ls_covariance_diag(self._h, var.ctypes.data, 0), "stmmqr_ls_covariance_diag")
         return var[:self.n]
+
+    def condest(self, kind: int = 1, iters: int = 0, with_vector: bool = False) -> dict:
+        """after solve(): the condition of A(:, live) from the R the object holds (stmmqr_ls_condest; HipQR.condest with ncol = n)"""
+        return _condest_dict(lambda out, v: lib.stmmqr_ls_condest(self._h, int(kind), int(iters), out, v, 0), "stmmqr_ls_condest", self.n,
+                             with_vector)
 
     def diagnostics(self):
         """after solve(): (leverages, variances) from ONE selected inversion (stmmqr_ls_leverage): the leverages of the m rows of A

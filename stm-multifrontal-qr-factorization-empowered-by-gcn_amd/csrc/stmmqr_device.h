@@ -176,6 +176,11 @@ struct RtDesc {
     int lcoff;               // offset of its live-column list in the level's list (ints)
 };
 
+// products with R and R' (stmmqr_rmult.hip; tests/test_gpu_rmult.py sits on both sides of each)
+#define STM_RM_ROWS 256      // R x: rows of a front per workgroup, a row per thread
+#define STM_RM_XC 256        // R x: entries of x staged in LDS per pass over a front's columns
+#define STM_RM_COLS 64       // R' y: columns of a front per workgroup, a half-wave per column
+
 #define STM_QB_ROWS 512      // rows of a front per workgroup of the split Q-apply (k_qbig_step)
 // split Q-apply (k_qbig_*): one entry per large front of a tree level
 struct QbDesc {

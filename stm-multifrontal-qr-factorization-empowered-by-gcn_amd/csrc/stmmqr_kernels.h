@@ -163,6 +163,19 @@ int stm_launch_rtsolve(const DevCtx &c, const int *flist, int nfr, const double 
                        int lds_bytes, hipStream_t st, int nb, const RhsBatch &B, int skip_rtbig = 0);
 int stm_launch_rtsolve_big(const DevCtx &c, const RtDesc *rd, int nq, int max_steps, int max_nslab, const double *Bp, double *U, double *Xr,
                            const int *rowbase, int *Lc, int *Rm, int *err, hipStream_t st, int nb, const RhsBatch &B);
+// products with R and R' on the resident factors (stmmqr_rmult.hip), a tree level per launch.  R x: X in R's column order (stride
+// B.x) -> Y in R's row order (stride B.w), max_slab = most row slabs (STM_RM_ROWS) of a front of the level.  R' y: every front's
+// column dots into its slots of U (stride B.u; absval: |R| and y = 1, one vector), max_slab = most column slabs (STM_RM_COLS);
+// then, once for all levels, z[j] = its slots in slot order (cp / slot: the transpose of Rj)
+int stm_launch_rmult(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *Rj, const int *rowbase, const double *X, double *Y,
+                     hipStream_t st, int nb, const RhsBatch &B);
+int stm_launch_rtmult_dots(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *rowbase, const double *Y, double *U, int absval,
+                           hipStream_t st, int nb, const RhsBatch &B);
+int stm_launch_rtmult_gather(const int *cp, const int *slot, const double *U, double *Z, int n, hipStream_t st, int nb, long long su, long long sz);
+// the reductions and maps of the condition estimate (stmmqr_rmult.hip: k_ce_reduce / k_ce_map / k_ce_vector list the `what` codes)
+int stm_launch_ce_reduce(int what, const double *a, const int *idx, const double *b, int r, double *out, hipStream_t st);
+int stm_launch_ce_map(int what, double *a, const int *idx, double *dst, int r, double d, hipStream_t st);
+int stm_launch_ce_vector(const double *x, const int *qfill, double *out, int ncol, double d, hipStream_t st);
 int stm_launch_panel_msg(void *const homes[6], const long long offs[6], const long long bytes[6], void *buf, int out, hipStream_t st);
 // subtree exchange: contribution blocks between plans as fixed-size messages, packed / unpacked on the device (stmmqr_pack.hip)
 struct StmFrontMsg { long long off, slot; int f, pad; };      // front f at buf + off: [8 | slot | fn - fp] doubles

@@ -228,6 +228,13 @@ int stmmqr_ls_covariance_entries(stmmqr_ls *ls, stm_long npairs, const stm_long 
     return stmmqr_plan_covariance_entries(ls->plan, ls->n, npairs, I, J, out, on_device);
 }
 
+// the condition of A(:, live) from the R of [A B] the object holds
+int stmmqr_ls_condest(stmmqr_ls *ls, int kind, int iters, double *out, double *v, int on_device)
+{
+    if (int e = ls_fit_ready(ls, "stmmqr_ls_condest")) return e;
+    return stmmqr_plan_condest(ls->plan, ls->n, kind, iters, out, v, on_device);
+}
+
 void stmmqr_ls_free(stmmqr_ls *ls) { delete ls; }
 
 }  // extern "C"

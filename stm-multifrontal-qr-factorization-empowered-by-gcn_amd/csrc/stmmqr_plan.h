@@ -253,6 +253,12 @@ struct stmmqr_plan {
     DevBuf<RtDesc> d_rtb;
     DevBuf<int> d_rtLc, d_rtRm;                     // live pivot columns of the level's split fronts (rtlc_ints) / their counts
     long long rtlc_ints = 1;
+    // products with R and R' (stmmqr_plan_rmult, stmmqr_plan_condest), all made at the first call that needs them: the transpose of
+    // Rj (column -> its slots of the pass-vector array, in slot order), per level the most row / column slabs of a front, and the
+    // condition estimate's vectors (two of n, one of m, the attaining vector, the live pivot columns, the scalars read back)
+    DevBuf<int> d_rmcp, d_rmslot, d_cepc;
+    std::vector<int> level_rm_rslab, level_rm_cslab;
+    DevBuf<double> d_ceA, d_ceB, d_ceY, d_ceV, d_ceS;
     DevBuf<int> d_Dq;
     DevBuf<QbDesc> d_qb;
     // grouped split Q-apply (k_qbig_step4): T4 of every group of four panels of every split front, built at the first Q-apply after a

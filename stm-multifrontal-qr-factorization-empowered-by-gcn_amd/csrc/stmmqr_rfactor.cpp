@@ -649,6 +649,271 @@ int stmmqr_plan_solve_minnorm(stmmqr_plan *plan, const double *B, stm_long ldb, 
     return end_resident_op(P);
 }
 
+// ---- products with R and R', and the condition estimate built on them (factors with or without H) ----
+namespace {
+// Once per plan, at the first product: per tree level the most row slabs (R x) and column slabs (R' y) of a front -- all R x needs
+int ensure_rmult(stmmqr_plan &P)
+{
+    const auto &LV = P.glevels[0];
+    if (P.level_rm_rslab.size() == LV.size()) return 0;
+    P.level_rm_rslab.assign(LV.size(), 0);
+    P.level_rm_cslab.assign(LV.size(), 0);
+    for (size_t l = 0; l < LV.size(); l++)
+        for (int q = 0; q < LV[l].n_all; q++) {
+            const FrontSym &s = P.fs[P.lists[LV[l].all_off + q]];
+            P.level_rm_rslab[l] = std::max(P.level_rm_rslab[l], (std::min(s.fp, s.fm_ub) + STM_RM_ROWS - 1) / STM_RM_ROWS);
+            P.level_rm_cslab[l] = std::max(P.level_rm_cslab[l], (s.fn + STM_RM_COLS - 1) / STM_RM_COLS);
+        }
+    return 0;
+}
+// ... and what R' y needs besides, at the first transposed product: the pass-vector array U of the R' solve and the transpose of Rj
+// (column j of R -> the slots Rp[f] + k with Rj = j, in slot order)
+int ensure_rtmult(stmmqr_plan &P)
+{
+    PASS(ensure_rmult(P));
+    LCHK(ensure_rt_buffers(P));
+    if (P.d_rmcp.p) return 0;
+    const long n = P.n;
+    std::vector<int> cp((size_t)n + 1, 0), slot((size_t)std::max(1L, P.rjsize), 0);
+    for (long p = 0; p < P.rjsize; p++) cp[(size_t)P.Rj[(size_t)p] + 1]++;
+    for (long j = 0; j < n; j++) cp[(size_t)j + 1] += cp[(size_t)j];
+    std::vector<int> fill(cp.begin(), cp.end() - 1);
+    for (long p = 0; p < P.rjsize; p++) slot[(size_t)fill[(size_t)P.Rj[(size_t)p]]++] = (int)p;
+    LCHK(P.d_rmslot.upload(slot, P.stream));
+    LCHK(P.d_rmcp.upload(cp, P.stream));
+    HIPCHK(hipStreamSynchronize(P.stream));                    // (cp / slot are local)
+    return 0;
+}
+// nb vectors X (device, R's column order, stride n) -> Y (device, R's row order, stride m) = R X; rows beyond the rank are zero
+int rmult_pass(stmmqr_plan &P, const double *X, double *Y, int nb)
+{
+    const RhsBatch B = rhs_strides(P);
+    const DevCtx c = res_ctx(P);
+    const auto &LV = P.glevels[0];
+    HIPCHK(hipMemsetAsync(Y, 0, (size_t)nb * (size_t)std::max(1L, P.m) * sizeof(double), P.stream));
+    for (size_t l = 0; l < LV.size(); l++) {
+        LCHK(level_to_front_form(P, l));
+        LCHK(stm_launch_rmult(c, P.d_lists.p + LV[l].all_off, LV[l].n_all, P.level_rm_rslab[l], P.d_Rj.p, P.d_rowbase.p, X, Y, P.stream, nb, B));
+    }
+    return 0;
+}
+// nb vectors Y (device, R's row order, stride m; rows beyond the rank are not read) -> Z (device, R's column order, stride n) = R' Y,
+// or with absval the column 1-norms of R (one vector, Y not read)
+int rtmult_pass(stmmqr_plan &P, const double *Y, double *Z, int nb, int absval = 0)
+{
+    const RhsBatch B = rhs_strides(P);
+    const DevCtx c = res_ctx(P);
+    const auto &LV = P.glevels[0];
+    for (size_t l = 0; l < LV.size(); l++) {
+        LCHK(level_to_front_form(P, l));
+        LCHK(stm_launch_rtmult_dots(c, P.d_lists.p + LV[l].all_off, LV[l].n_all, P.level_rm_cslab[l], P.d_rowbase.p, Y, P.d_U.p, absval, P.stream, nb, B));
+    }
+    return stm_launch_rtmult_gather(P.d_rmcp.p, P.d_rmslot.p, P.d_U.p, Z, (int)P.n, P.stream, nb, B.u, P.n);
+}
+// does the plan hold the whole tree in one group (what the selected inversion asks as well)
+bool holds_whole_tree(const stmmqr_plan &P)
+{
+    bool whole = P.glevels.size() == 1;
+    for (long f = 0; f < P.nf && whole; f++) whole = P.group[(size_t)f] == 0 && !((size_t)f < P.shared.size() && P.shared[(size_t)f]);
+    return whole;
+}
+}  // namespace
+
+// Y = R X (trans 0) or R' X (trans 1) with the whole rank x n factor on the device; see include/stmmqr_hip.h
+int stmmqr_plan_rmult(stmmqr_plan *plan, int trans, const double *X, stm_long ldx, double *Y, stm_long ldy, stm_long nrhs, int permuted,
+                      int on_device)
+{
+    PASS(check_factored(plan));
+    if ((trans != 0 && trans != 1) || !X || !Y || nrhs < 0) return fail(STMMQR_ERR_INVALID, "bad rmult arguments");
+    stmmqr_plan &P = *plan;
+    const long m = P.m, n = P.n, xrows = trans ? m : n, yrows = trans ? n : m;
+    if (ldx < xrows || ldy < yrows) return fail(STMMQR_ERR_INVALID, "bad leading dimension");
+    PASS(begin_resident_op(P));
+    if (nrhs == 0 || yrows == 0) return 0;
+    hipStream_t st = P.stream;
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
+    PASS(trans ? ensure_rtmult(P) : ensure_rmult(P));
+    LCHK(grow(P.d_Xall, (size_t)(std::max(1L, xrows) * nrhs)));
+    LCHK(grow(P.d_Yall, (size_t)(yrows * nrhs)));
+    PASS(copy_cols(P.d_Xall.p, xrows, X, ldx, xrows, nrhs, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    const int *qf = (!permuted && P.has_qfill) ? P.d_Qfill.p : nullptr;
+    PASS(for_each_batch(P, nrhs, [&](stm_long j, int nb) -> int {
+        if (!trans) {
+            LCHK(stm_launch_perm(P.d_Xall.p + j * n, qf, P.d_Xs.p, (int)n, 0, st, nb, n, n));                 // x[k] = X[Qfill[k]]
+            return rmult_pass(P, P.d_Xs.p, P.d_Yall.p + j * m, nb);
+        }
+        PASS(rtmult_pass(P, P.d_Xall.p + j * m, P.d_Xs.p, nb));
+        return stm_launch_perm(P.d_Xs.p, qf, P.d_Yall.p + j * n, (int)n, 1, st, nb, n, n);                   // Y[Qfill[k]] = z[k]
+    }));
+    LCHK(download_cols(P, P.d_Yall, Y, ldy, yrows, nrhs, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    return end_resident_op(P);
+}
+
+// The condition of R over its live pivot columns, estimated on the device; see include/stmmqr_hip.h.  Vectors: the r-vector of the
+// live pivot columns lives either in an n-vector in R's column order (entry i at pc[i], zero elsewhere: what R x reads, what R \ and
+// R' y write) or in the first r entries of an m-vector in R's row order (what R \ and R' y read, what R x and R' \ write).  With
+// ncol < n the trailing columns stay zero in every input and are never read from an output: R [x; 0] = R11 x, R \ [y; 0] = R11 \ y,
+// and the leading rows of R' \ [z; *] are R11' \ z.
+int stmmqr_plan_condest(stmmqr_plan *plan, stm_long ncol, int kind, int iters, double *out, double *v, int on_device)
+{
+    PASS(check_factored(plan));
+    if (!out) return fail(STMMQR_ERR_INVALID, "condest: out is NULL");
+    stmmqr_plan &P = *plan;
+    const long m = P.m, n = P.n;
+    if (ncol < 0 || ncol > n)
+        return fail(STMMQR_ERR_INVALID, "condest: ncol = " + std::to_string(ncol) + " is not between 0 and the " + std::to_string(n) + " columns of the plan");
+    if (kind != 1 && kind != 2) return fail(STMMQR_ERR_INVALID, "condest: kind = " + std::to_string(kind) + " is neither 1 (one-norm) nor 2 (two-norm)");
+    if (ncol < n) PASS(check_carried_view(P, ncol));
+    if (!holds_whole_tree(P))
+        return fail(STMMQR_ERR_INVALID, "condest: the plan does not hold the whole tree in one group (groups were set, or fronts are imported or shared)");
+    PASS(begin_resident_op(P));
+    hipStream_t st = P.stream;
+    if (iters <= 0) iters = 8;
+    // the live pivot columns among the first ncol, in R's column order = in the order of the rows of R
+    std::vector<char> rd((size_t)std::max(1L, (long)ncol), 0);
+    if (ncol > 0) HIPCHK(hipMemcpyAsync(rd.data(), P.d_Rdead.p, (size_t)ncol, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<int> pc;
+    for (long j = 0; j < ncol; j++)
+        if (!rd[(size_t)j]) pc.push_back((int)j);
+    const int r = (int)pc.size();
+    double res[8] = {1.0, 0.0, 0.0, 0.0, (double)r, (double)kind, 0.0, 0.0};
+    auto give = [&](double *dst, const double *src, size_t cnt) -> int {      // a host array to the caller's, host or device
+        if (on_device) { HIPCHK(hipMemcpyAsync(dst, src, cnt * sizeof(double), hipMemcpyHostToDevice, st)); HIPCHK(hipStreamSynchronize(st)); }
+        else memcpy(dst, src, cnt * sizeof(double));
+        return 0;
+    };
+    if (r == 0) {
+        if (v && ncol > 0) { const std::vector<double> z((size_t)ncol, 0.0); PASS(give(v, z.data(), z.size())); }
+        return give(out, res, 8);
+    }
+    HIPCHK(hipMemsetAsync(P.d_err.p, 0, sizeof(int), st));
+    PASS(ensure_rtmult(P));
+    PASS(ensure_rt_any(P));
+    const size_t nn = (size_t)std::max(1L, n), mm = (size_t)std::max(1L, m);
+    LCHK(grow(P.d_ceA, nn)); LCHK(grow(P.d_ceB, nn)); LCHK(grow(P.d_ceV, nn)); LCHK(grow(P.d_ceY, mm)); LCHK(grow(P.d_ceS, 8));
+    if (P.d_cepc.n < (size_t)r) LCHK(P.d_cepc.alloc((size_t)r));
+    HIPCHK(hipMemcpyAsync(P.d_cepc.p, pc.data(), (size_t)r * sizeof(int), hipMemcpyHostToDevice, st));
+    double *dA = P.d_ceA.p, *dB = P.d_ceB.p, *dV = P.d_ceV.p, *dY = P.d_ceY.p, *dS = P.d_ceS.p;
+    const int *dpc = P.d_cepc.p;
+    double sc[4] = {0, 0, 0, 0};
+    auto scalars = [&]() -> int {                                              // the few scalars the host steers by
+        HIPCHK(hipMemcpyAsync(sc, dS, sizeof(sc), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    };
+    // the r-vector h (host) into the zeroed m-vector dY / the zeroed n-vector dst
+    auto put_rows = [&](const std::vector<double> &h) -> int {
+        HIPCHK(hipMemsetAsync(dY, 0, mm * sizeof(double), st));
+        HIPCHK(hipMemcpyAsync(dY, h.data(), (size_t)r * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));                                      // (h is pageable)
+        return 0;
+    };
+    // dY (R's row order, zero beyond r) -> d_Xs = R \ dY
+    auto solve_r = [&]() -> int {
+        LCHK(stm_launch_perm(dY, P.d_Wmap.p, P.d_W.p, (int)m, 0, st, 1, m, m));
+        return rsolve_vector(P, 1);
+    };
+    std::vector<double> safe((size_t)r, 1.0);                                  // x_i = (-1)^i (1 + i / (r - 1))
+    for (int i = 0; i < r && r > 1; i++) safe[(size_t)i] = ((i & 1) ? -1.0 : 1.0) * (1.0 + (double)i / (double)(r - 1));
+    double vnorm = 1.0;                                                        // v = dV / vnorm
+    if (kind == 1) {
+        // |R_live|_1: exact, the largest column sum of |R| over the live columns
+        PASS(rtmult_pass(P, dY, dB, 1, 1));
+        LCHK(stm_launch_ce_reduce(2, dB, dpc, nullptr, r, dS, st));
+        PASS(scalars());
+        res[1] = sc[0];
+        // Hager's iteration in Higham's form on R_live^-1
+        double est = 0.0;
+        int rounds = 0, jprev = -1;
+        PASS(put_rows(std::vector<double>((size_t)r, 1.0 / (double)r)));
+        for (int round = 1; round <= 5; round++) {
+            rounds = round;
+            PASS(solve_r());                                                   // y = R \ x
+            LCHK(stm_launch_ce_reduce(0, P.d_Xs.p, dpc, nullptr, r, dS, st));
+            PASS(scalars());
+            if (round > 1 && !(sc[0] > est)) break;                            // the estimate does not grow
+            est = vnorm = sc[0];
+            HIPCHK(hipMemcpyAsync(dV, P.d_Xs.p, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+            if (round == 5) break;
+            LCHK(stm_launch_ce_map(0, P.d_Xs.p, dpc, nullptr, r, 0.0, st));    // xi = sign(y)
+            PASS(rt_pass_any(P, 1));                                           // z = R' \ xi: the first r rows of d_Xr
+            LCHK(stm_launch_ce_reduce(3, P.d_Xr.p, nullptr, dY, r, dS, st));
+            PASS(scalars());
+            const int j = (int)sc[2];
+            if (sc[1] <= sc[3] || j == jprev) break;                           // |z|_inf <= z'x, or the arg-max repeats
+            jprev = j;
+            const double one = 1.0;
+            HIPCHK(hipMemsetAsync(dY, 0, (size_t)r * sizeof(double), st));
+            HIPCHK(hipMemcpyAsync(dY + j, &one, sizeof(double), hipMemcpyHostToDevice, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        PASS(put_rows(safe));                                                  // the safeguard vector
+        PASS(solve_r());
+        LCHK(stm_launch_ce_reduce(0, P.d_Xs.p, dpc, nullptr, r, dS, st));
+        PASS(scalars());
+        const double est2 = 2.0 * sc[0] / (3.0 * (double)r);
+        if (est2 > est) {
+            est = est2; vnorm = sc[0];
+            HIPCHK(hipMemcpyAsync(dV, P.d_Xs.p, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+        }
+        res[2] = est; res[3] = (double)rounds;
+    } else {
+        double s2 = 0.0;
+        for (double t : safe) s2 += t * t;
+        s2 = std::sqrt(s2);
+        std::vector<double> start(safe);
+        for (double &t : start) t /= s2;
+        // |R_live|_2: power iteration on R'R, x <- R'(R x) / |R'(R x)|, estimate sqrt |R'(R x)|
+        PASS(put_rows(start));
+        HIPCHK(hipMemsetAsync(dA, 0, nn * sizeof(double), st));
+        LCHK(stm_launch_ce_map(2, dY, dpc, dA, r, 0.0, st));
+        double lam = 0.0;
+        for (int it = 0; it < iters; it++) {
+            PASS(rmult_pass(P, dA, dY, 1));
+            PASS(rtmult_pass(P, dY, dB, 1));
+            LCHK(stm_launch_ce_reduce(1, dB, dpc, nullptr, r, dS, st));
+            PASS(scalars());
+            lam = std::sqrt(sc[0]);
+            if (!(lam > 0.0)) break;
+            LCHK(stm_launch_ce_map(1, dB, dpc, dA, r, lam, st));
+        }
+        res[1] = std::sqrt(lam);
+        // |R_live^-1|_2: the same on (R'R)^-1, x <- R \ (R' \ x) / |.|; the estimate is 1 / |R_live v|_2 of the last iterate v
+        PASS(put_rows(start));
+        HIPCHK(hipMemsetAsync(dV, 0, nn * sizeof(double), st));
+        LCHK(stm_launch_ce_map(2, dY, dpc, dV, r, 0.0, st));
+        int made = 0;                                                          // solve pairs whose result became the iterate
+        for (int it = 0; it < iters; it++) {
+            HIPCHK(hipMemcpyAsync(P.d_Xs.p, dV, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+            PASS(rt_pass_any(P, 1));                                           // t = R' \ x: the first r rows of d_Xr
+            HIPCHK(hipMemcpyAsync(dY, P.d_Xr.p, (size_t)r * sizeof(double), hipMemcpyDeviceToDevice, st));   // (dY is zero beyond r)
+            PASS(solve_r());                                                   // w = R \ t
+            LCHK(stm_launch_ce_reduce(1, P.d_Xs.p, dpc, nullptr, r, dS, st));
+            PASS(scalars());
+            const double mu = std::sqrt(sc[0]);
+            if (!(mu > 0.0) || !std::isfinite(mu)) break;
+            LCHK(stm_launch_ce_map(1, P.d_Xs.p, dpc, dV, r, mu, st));
+            made++;
+        }
+        PASS(rmult_pass(P, dV, dY, 1));
+        LCHK(stm_launch_ce_reduce(1, dY, nullptr, nullptr, r, dS, st));
+        PASS(scalars());
+        res[2] = 1.0 / std::sqrt(sc[0]);
+        res[3] = (double)made;
+    }
+    res[0] = res[1] * res[2];
+    if (v) {
+        // in the caller's column order, zeros on dead columns (R \ leaves them zero), unit norm of the kind
+        double *dv = on_device ? v : dB;
+        HIPCHK(hipMemsetAsync(dv, 0, (size_t)ncol * sizeof(double), st));
+        LCHK(stm_launch_ce_vector(dV, P.has_qfill ? P.d_Qfill.p : nullptr, dv, (int)ncol, vnorm, st));
+        if (!on_device) HIPCHK(hipMemcpyAsync(v, dv, (size_t)ncol * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    PASS(end_resident_op(P));
+    return give(out, res, 8);
+}
+
 // ---- products with A and the corrected seminormal equations (factors with or without H) ----
 namespace {
 // Y = A X (trans 0: X n x nrhs, Y m x nrhs), A' X (trans 1: X m, Y n), or with B (trans 0 only) Y = B - A X for the m x n matrix with
@@ -837,9 +1102,7 @@ int selected_inverse(stmmqr_plan *plan, stm_long ncol, double *var, int on_devic
     if (ncol < 0 || ncol > n)
         return fail(STMMQR_ERR_INVALID, "covariance: ncol = " + std::to_string(ncol) + " is not between 0 and the " + std::to_string(n) + " columns of the plan");
     if (ncol < n) PASS(check_carried_view(P, ncol));
-    bool whole = P.glevels.size() == 1;
-    for (long f = 0; f < P.nf && whole; f++) whole = P.group[(size_t)f] == 0 && !((size_t)f < P.shared.size() && P.shared[(size_t)f]);
-    if (!whole)
+    if (!holds_whole_tree(P))
         return fail(STMMQR_ERR_INVALID, "covariance: the plan does not hold the whole tree in one group (groups were set, or fronts are imported or shared)");
     PASS(host_checks(P));
     PASS(begin_resident_op(P));
