@@ -187,7 +187,7 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
             const bool over_lds = stm_lds_qapply(fm, fn) > STM_RES_LDS_MAX || stm_lds_rsolve(fp, fn) > STM_RES_LDS_MAX;
             s.qbig = ((fm * fn >= qbig_min || over_lds) && fn >= 1) ? 1 : 0;
             // R' x = b: the one-workgroup kernel keeps the front's u and x in LDS (6 550 columns of a square-ish front, 10 890 of a
-            // short wide one); a front beyond that is split over its columns (k_rtbig_*) by the pass that knows how, rt_pass_any.
+            // short wide one); a front beyond that is split over its columns (k_rtbig_*) by the pass that knows how, rt_pass in mode RT_SPLIT.
             // STMMQR_RTBIG_MIN splits smaller ones too
             s.rtbig = (stm_lds_rtsolve(fp, fm, fn) > STM_RES_LDS_MAX || fm * fn >= knobs::num(knobs::K_RTBIG_MIN)) ? 1 : 0;
         }
@@ -604,9 +604,7 @@ int stmmqr_factorize_begin(stmmqr_plan *plan, const stm_long *Ap, const stm_long
     P.stats = stmmqr_stats();
     P.stats.ms_host = host_ms_plan;
     P.factored = false;
-    P.rowmap_ready = false;
-    P.scr_valid = false;
-    P.t4_valid = false;
+    P.res.new_factorization();
     P.evused = 0;
     P.begun = true;
     P.first_group = true;

@@ -15,7 +15,7 @@ void stm_cc_set_status(stm_sparse_common *cc, int code);
 // SparseCore_malloc / SparseCore_free semantics (src/core/SparseCore_common.c:603-655): counted in cc->malloc_count / memory_inuse
 void *stm_cc_malloc(size_t n, size_t size, stm_sparse_common *cc);
 void stm_cc_free(size_t n, size_t size, void *p, stm_sparse_common *cc);
-// a device copy of a caller's CSC matrix for products with it (k_spmv; stmmqr_rfactor.cpp): stmmqr_sparseqr_solve_seminormal
+// a device copy of a caller's CSC matrix for products with it (k_spmv; stmmqr_seminormal.cpp): stmmqr_sparseqr_solve_seminormal
 typedef struct stm_aop stm_aop;
 int stm_aop_create(int device, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax, stm_aop **out);
 void stm_aop_destroy(stm_aop *op);

@@ -3,7 +3,9 @@
 //   stmmqr_schedule.cpp  arenas, the timeline allocator, the step timeline of every front group (stm_build_schedule)
 //   stmmqr_run.cpp       the step scheduler (stm_run_schedule: one step, serial, look-ahead, passengers), the pack pass
 //   stmmqr_multi.cpp     contribution blocks / panels in and out of a plan, shared fronts, the RCCL transport
-//   stmmqr_rfactor.cpp   Q-apply and triangular solves on the resident factors
+//   stmmqr_rfactor.cpp   Q-apply and triangular solves on the resident factors; with stmmqr_rcond.cpp (products with R,
+//                        condition estimate), stmmqr_rcov.cpp (selected inverse), stmmqr_seminormal.cpp (products with A, seminormal
+//                        solves) and the pure stmmqr_restables.cpp: stmmqr_resident.h
 //   stmmqr_seam.cpp      the drop-in seam qr_factorize with the reference's structs, its plan cache
 #pragma once
 #include <hip/hip_runtime.h>
@@ -92,10 +94,7 @@ template <class T> struct DevBuf {
 // column rj and the position rq of its value in A's storage) for A x.  Built on the host by stm_row_form (stmmqr_internal.h).
 struct AIndexDev { DevBuf<int> cp, ci, rp, rj, rq; };
 
-struct Level {                           // tree level of a group: what the solve / Q-apply kernels walk (f1)
-    int all_off = 0, n_all = 0;          // every front of the level (small first, then big by npanels desc)
-    int n_small = 0, n_big = 0;
-};
+#include "stmmqr_resident.h"          // (Level, ResidentState: needs DevBuf)
 
 // One step of the factorization timeline.  Every front starts at the step after the last of its children has finished
 // (a small front takes one step, a big one a step per panel), so a front deep in a short branch does not wait for the
@@ -174,9 +173,6 @@ struct stmmqr_plan {
     std::vector<long long> rh_est_front; // ... per front (keepH = 0: the arena holds those of the fronts that do not keep their slab)
     int rh_grow = 0;                     // 0: the arena is sized from that estimate; 1: from the hard bounds (it overflowed once)
     double rh_est_scale = 1.0;           // ... times STMMQR_RH_EST_SCALE, read once when the plan is created (tests shrink the estimate)
-    long long scr_doubles = 0;           // scratch of the resident-factor operations: the widest tree level in front form
-    std::vector<FrontSym> fs_scr;        // FrontSym with foff into that scratch (kept fronts: their own slab, relative to it)
-    bool scr_all = false, scr_valid = false;   // the scratch holds every front (rebuilt once per factorization) / is up to date
     bool overflowed = false;             // a factorization did not fit the R+H arena at its hard bound: this plan does not recycle
     bool early_end = false;              // the schedule of group 0 stops every front at the panel where it is expected to run out of rows
     bool full_schedule = false;          // ... it did not hold once (rank-deficient fronts): this plan schedules every panel from now on
@@ -214,8 +210,7 @@ struct stmmqr_plan {
     DevBuf<long long> d_Rboff, d_total;
     DevBuf<long long> d_rhtop, d_fin;    // slab recycling: {bump pointer, overflow word}; Post-order offsets of the packed blocks
     DevBuf<char> d_kept;
-    DevBuf<double> d_scr, d_bounce;      // resident-factor scratch (one tree level in front form); download window
-    DevBuf<FrontSym> d_fs_scr;
+    DevBuf<double> d_bounce;             // download window
     DevBuf<unsigned long long> d_dbg, d_amax;
     DevBuf<double> d_sig;                           // {sg, 1/sg}: magnitude guard of the panel kernels
     DevBuf<char> d_Rdead;
@@ -223,13 +218,6 @@ struct stmmqr_plan {
     AIndexDev a_idx;
     std::vector<int> h_smap;                    // host copy of d_smap (what those forms are built from)
     bool a_index_ready = false;
-    DevBuf<double> d_csB, d_csX, d_csR, d_csZ, d_csY, d_csD, d_csN;   // the seminormal solve's vectors (grown on demand)
-    // stmmqr_plan_solve_carried: the view of the factorization that ends at column n (FrontSym with fp cut back to the A pivots,
-    // FrontNum with the live A pivots as rank), the fronts that hold B pivots, the residual norms
-    DevBuf<FrontSym> d_fs_car;
-    DevBuf<FrontNum> d_fnum_car;
-    DevBuf<int> d_carlist;
-    DevBuf<double> d_carN;
 
     // results of the last factorization
     bool factored = false, begun = false, first_group = true;
@@ -239,60 +227,17 @@ struct stmmqr_plan {
     long long rh_total = 0;
     long rank = 0;
     std::vector<FrontNum> h_fnum;
-    // Q-apply / solve on the resident factors
-    DevBuf<int> d_Rj, d_PLinv, d_Qfill, d_Wmap, d_err;
-    DevBuf<double> d_W, d_Xs, d_Io, d_Xf, d_Wq, d_Xall, d_Yall, d_U, d_Xr;
-    DevBuf<int> d_rowbase;                          // rows of R above each front (R rows are numbered front by front)
-    std::vector<int> level_lds_rt;                  // dynamic LDS of k_rtsolve per level
-    // the R' pass that takes fronts of any width (rt_pass_any): per level, the fronts with FrontSym::rtbig (descriptors in d_rtb
-    // from off), their most blocks of 32 pivot columns and column slabs (plan time) / blocks of the factorization held, and the
-    // dynamic LDS k_rtsolve needs for the other fronts of the level
-    struct RtLevel { int off = 0, n = 0, max_steps = 0, max_nslab = 0, live_steps = 0, lds_small = 0; };
-    std::vector<RtLevel> level_rtbig;
-    std::vector<RtDesc> h_rtb;
-    DevBuf<RtDesc> d_rtb;
-    DevBuf<int> d_rtLc, d_rtRm;                     // live pivot columns of the level's split fronts (rtlc_ints) / their counts
-    long long rtlc_ints = 1;
-    // products with R and R' (stmmqr_plan_rmult, stmmqr_plan_condest), all made at the first call that needs them: the transpose of
-    // Rj (column -> its slots of the pass-vector array, in slot order), per level the most row / column slabs of a front, and the
-    // condition estimate's vectors (two of n, one of m, the attaining vector, the live pivot columns, the scalars read back)
-    DevBuf<int> d_rmcp, d_rmslot, d_cepc;
-    std::vector<int> level_rm_rslab, level_rm_cslab;
-    DevBuf<double> d_ceA, d_ceB, d_ceY, d_ceV, d_ceS;
-    DevBuf<int> d_Dq;
-    DevBuf<QbDesc> d_qb;
-    // grouped split Q-apply (k_qbig_step4): T4 of every group of four panels of every split front, built at the first Q-apply after a
-    // factorization (t4_valid); t4_ok: the buffers exist (they are allocated at that first use; no room: the per-panel launches stay)
-    std::vector<Qt4ItemHost> t4items;
-    std::vector<int> t4fronts;
-    std::vector<long long> t4dqo, qbt4off;
-    long long t4_doubles = 0, dq4_ints = 0, wq4_doubles = 0;
-    DevBuf<Qt4ItemHost> d_t4items;
-    DevBuf<int> d_t4fronts, d_Dq4;
-    DevBuf<long long> d_t4dqo, d_qbt4off;
-    DevBuf<double> d_T4, d_Wq4;
-    bool t4_valid = false, t4_ok = false, t4_tried = false;
-    struct QbLevel { int off = 0, n = 0, max_np = 0, max_nslab = 0, max_fm = 0, max_rsteps = 0, t4i_off = 0, t4i_n = 0;
-                     int live_np = 0, live_rsteps = 0; };     // (live_*: of the current factorization, ensure_rowmap)
-    std::vector<QbDesc> h_qb;            // host copy of d_qb (np_live is refreshed per factorization)
-    std::vector<char> t4_level_valid;          // T4 of the level's split fronts is built (per level: with per-level scratch only the
-                                               //  level at hand is in front form)
-    DevBuf<int> d_Rm;                               // rows of R (live pivots) of the split fronts of a level (k_rbig_*)
-    // several right-hand sides per launch (RhsBatch, stmmqr_kernels.h): the per-vector buffers hold rhs_cap vectors at these strides
-    int rhs_cap = 1;
-    long long xf_doubles = 1, wq_doubles = 1;
-    std::vector<QbLevel> level_qbig;               // descriptors (d_qb) of the fronts of each level that take the split Q-apply
+    ResidentState res;                   // everything the operations on the resident factors keep (stmmqr_resident.h)
     hipGraphExec_t graph_exec = nullptr;           // options.use_graph: the captured schedule of group 0
     double graph_tol = 0; int graph_ntol = 0, graph_dbg = 0; unsigned long long graph_opt = 0; long graph_nlaunch = 0;
     long sched_gen = 0, graph_gen = -1;            // schedule generation (bumped by every stm_build_schedule) / the captured one
-    bool rowmap_ready = false;         // d_Wmap belongs to the factorization currently held
-    std::vector<int> level_lds_qa, level_lds_qa_all, level_lds_rs;   // dynamic LDS of k_qapply(_t) / k_rsolve per level of group 0
-                                                                     // (_all: the unblocked kernel takes the split fronts too)
     double last_tol = 0;
     long last_ntol = 0;
     stmmqr_stats stats = {};
 
-    // device memory held right now (every DevBuf of the plan)
+    // device memory held right now: the buffers of the factorization and the index of A; of the resident-factor operations only the
+    // recycling scratch and the carried solve's view.  Their maps, work vectors, staging and T4 buffers (the rest of `res`) are not
+    // counted: stats.device_bytes reports this number, the footprint of the factorization
     double device_bytes() const
     {
         double b = 0;
@@ -301,9 +246,9 @@ struct stmmqr_plan {
         add(d_Wp); add(d_Wp2); add(d_tslot); add(d_Sp); add(d_Sjrel); add(d_Sj0); add(d_Sleft); add(d_Child); add(d_Rjrel);
         add(d_Stair); add(d_Hii); add(d_Cmap); add(d_Cursor); add(d_lists); add(d_smap); add(d_Rhoff); add(d_wlists);
         add(d_wcnt); add(d_wcnt2); add(d_wflag); add(d_wflag2); add(d_Rboff); add(d_Rdead); add(d_Ypend); add(d_ypoff);
-        add(d_rhtop); add(d_fin); add(d_kept); add(d_scr); add(d_bounce); add(d_fs_scr);
+        add(d_rhtop); add(d_fin); add(d_kept); add(res.sched.d_scr); add(d_bounce); add(res.sched.d_fs_scr);
         add(a_idx.cp); add(a_idx.ci); add(a_idx.rp); add(a_idx.rj); add(a_idx.rq);
-        add(d_fs_car); add(d_fnum_car); add(d_carlist); add(d_carN);
+        add(res.call.d_fs_car); add(res.call.d_fnum_car); add(res.call.d_carlist); add(res.call.d_carN);
         return b;
     }
     DevCtx ctx() const { return ctx((int)knobs::num(knobs::K_DBG)); }

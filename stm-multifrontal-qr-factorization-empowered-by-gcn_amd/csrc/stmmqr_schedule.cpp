@@ -73,7 +73,7 @@ int stm_upload_recycle(stmmqr_plan &P)
     if (!P.recycle) return 0;
     LCHK(P.d_kept.upload(P.kept, P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));
-    P.d_scr.release();                                        // (allocated by the first resident-factor operation: ensure_scratch)
+    P.res.sched.d_scr.release();                                     // (allocated by the first resident-factor operation: ensure_scratch)
     P.d_RH.release();                                         // (the arena follows with the front arenas: stm_ensure_arenas)
     return 0;
 }
@@ -634,17 +634,18 @@ struct Planner {
             }
         }
         // scratch of the resident-factor operations: every tree level in front form, one level at a time
-        P.fs_scr = P.fs;
-        P.scr_doubles = 1;
+        ResidentState::Schedule &R = P.res.sched;
+        R.fs_scr = P.fs;
+        R.scr_doubles = 1;
         for (size_t l = 0; l < LV.size(); l++) {
             long long o = 0;
             for (int q = 0; q < LV[l].n_all; q++) {
                 const int f = P.lists[(size_t)(LV[l].all_off + q)];
                 if (P.kept[(size_t)f]) continue;
-                P.fs_scr[(size_t)f].foff = o;
+                R.fs_scr[(size_t)f].foff = o;
                 o += slab(f);
             }
-            P.scr_doubles = std::max(P.scr_doubles, o);
+            R.scr_doubles = std::max(R.scr_doubles, o);
         }
     }
 

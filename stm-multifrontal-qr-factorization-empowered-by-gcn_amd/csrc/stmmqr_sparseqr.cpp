@@ -400,7 +400,7 @@ int stmmqr_sparseqr_set_keep_h(stmmqr_qr *qr, int keep)
     return 0;
 }
 
-// dimensions of the whole problem (stmmqr_sparseqr_solve_seminormal, stmmqr_rfactor.cpp); 0 or STMMQR_ERR_INVALID before numeric
+// dimensions of the whole problem (stmmqr_sparseqr_solve_seminormal, stmmqr_seminormal.cpp); 0 or STMMQR_ERR_INVALID before numeric
 int stm_sparseqr_dims(const stmmqr_qr *qr, stm_long *m, stm_long *n)
 {
     if (!qr || !qr->plan) return STMMQR_ERR_INVALID;
@@ -573,7 +573,7 @@ int stmmqr_sparseqr_solve(stmmqr_qr *qr, int system, const double *B, stm_long l
 // ---- minimum-2-norm solution of A x = b on the QR object of A': x = Q (R' \ (E' b)).  With singletons: the host stage through R1 as
 //      in system 3 above, the multifrontal part on the device in one call (no limit on a front's width), then the row scatter of
 //      QR_QX as in stmmqr_sparseqr_qmult.  This file is host code only (it is also built without the device half of the library),
-//      so the plan's solve comes in as `solve`: stmmqr_sparseqr_min2norm itself is in stmmqr_rfactor.cpp ----
+//      so the plan's solve comes in as `solve`: stmmqr_sparseqr_min2norm itself is in stmmqr_seminormal.cpp ----
 int stm_sparseqr_min2norm(stmmqr_qr *qr, const double *B, stm_long ldb, stm_long nrhs, double *X, stm_long ldx, stm_minnorm_fn solve)
 {
     if (!qr || !B || !X || nrhs < 0) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_min2norm: bad arguments");

@@ -62,7 +62,7 @@ WIDE = [s for s in SHAPES if s[0] < s[1]]
 
 
 def rt_fits(m, n):
-    """level_lds_rt of a dense one-front plan (ensure_rowmap): the one-workgroup R' solve is refused beyond 128 KB"""
+    """LevelTables::lds_rt of a dense one-front plan (restab::level_tables): the one-workgroup R' solve is refused beyond 128 KB"""
     return (((n + 1) & ~1) + ((min(n, max(m, 1)) + 2) & ~1)) * 8 + n * 4 + 32 <= LDS_MAX
 
 
