@@ -534,7 +534,53 @@ __global__ __launch_bounds__(NT, 2) void k_upd_f(DevCtx c, const int *__restrict
 // ticket; the last arriver raises the flag; then EVERY slab workgroup adds the partials in slab order, builds T (dev_T_from_gram)
 // and T'W for itself -- redundant arithmetic instead of a second hand-off -- and applies from the registers.
 // Arithmetic = k_upd_w (Gram block + block 0) + k_upd_c exactly: the same bits.
+//
+// LDS (STM_B0_LDS_DOUBLES; two workgroups per CU by registers, so 80 KB each are there): FOUR chunk images of BN * VS doubles, img(0) ..
+// img(3), as two pairs {img(0), img(1)} and {img(2), img(3)}, then Ws.  Both tile phases alternate between the pairs, so a chunk's
+// LDS writes run beside the MFMAs of the chunk before it and every chunk costs ONE barrier (round 5: two in phase 1, three in
+// phase 2, each LDS round trip exposed).  B(q) below is the barrier that ends turn q of a phase's loop.
+//   phase 1, chunk q: V and C images = pair q & 1.  Turn q reads pair q & 1 (MFMAs) and writes chunk q + 1 into the other pair, then
+//     B(q).  The pair written in turn q was last read in turn q - 1, before B(q - 1); the pair read in turn q was written in turn
+//     q - 1 (chunk 0: before the loop, with a barrier of its own), before B(q - 1).
+//   between the phases s_G / s_W1 live in img(0) and s_T in img(1), as before; pair 1 is idle there.
+//   phase 2, chunk q: V image and product image = pair (q + 1) & 1 -- chunk 0 takes pair 1, so its V image is written while T'W
+//     is formed out of pair 0, and the barrier behind Ws serves both.  C never goes through LDS: the thread that loaded a row's
+//     eight entries still holds them (ck[q].c), V W2 comes back from the MFMA layout through the product image and the thread
+//     subtracts and stores from registers (dev_upd_c_h2's form; C - (V W2) with the same operands: the same bits).  Turn q writes
+//     V(q + 1) into the other pair's V image, runs the MFMAs on V(q) and Ws, writes the product image of its own pair, B(q), then
+//     reads the product image and stores.  V image of a pair: written in turn q, read by the MFMAs of turn q + 1 [after B(q)],
+//     written again in turn q + 2 [after B(q + 1), which every reader has passed].  Product image of a pair: written in turn q before
+//     B(q), read after B(q) and before the reader arrives at B(q + 1), written again in turn q + 2, after B(q + 1).  Turn 0 writes
+//     img(0) (s_G / s_W1) and turn 1 img(1) (s_T): every reader of those is behind the barrier after Ws.
+// The rider role of the launch (dev_upd_w_rider) uses img(0) and img(1) only.
 // ------------------------------------------------------------------------------------------------
+#define STM_B0_LDS_DOUBLES (4 * BN * VS + STM_NB * WS)
+// K ordered sums side by side: v[k] = p[k][0] + p[k][stride] + ... (n terms), every one in THAT order from +0.0 exactly as stm_ordered_sum
+// forms it (a padded term is +0.0: exact), with the loads of U terms of all K sums in flight together -- one memory round trip per U
+// terms for the K sums, where K calls of stm_ordered_sum take K round trips one after the other.
+template <int K, int U>
+__device__ __forceinline__ void stm_ordered_sums(double (&v)[K], const double *const (&p)[K], long long stride, int n)
+{
+#pragma unroll
+    for (int k = 0; k < K; k++) v[k] = 0;
+    for (int q = 0; q < n; q += U) {
+        double t[K][U];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const double x = ld_agent(p[k] + (long long)min(q + u, n - 1) * stride);
+                t[k][u] = (q + u < n) ? x : 0.0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+#pragma unroll
+            for (int u = 0; u < U; u++) v[k] += t[k][u];
+        }
+    }
+}
+
 __device__ __forceinline__ void dev_k_upd_b0(const DevCtx &c, const int *__restrict__ flist, const int *__restrict__ plist, double *Wp,
                                              const long long *__restrict__ wpoff, int *wcnt, int *wflag, int epoch, int sl, int fi,
                                              double *dyn_lds)
@@ -546,47 +592,73 @@ __device__ __forceinline__ void dev_k_upd_b0(const DevCtx &c, const int *__restr
     unsigned long long tl0 = tl ? wall_clock64() : 0;
 #define B0TL(k) do { if (tl) { const unsigned long long t1 = wall_clock64(); atomicAdd(&c.dbgbuf[48 + (k)], t1 - tl0); tl0 = t1; } } while (0)
     const int f = flist[fi], p = plist[fi];
-    const FrontSym s = c.fs[f];
-    if (p >= s.npanels) return;
-    FrontNum *num = &c.fnum[f];
-    const PanelDesc *pd = &num->pd[STM_PDI(p)];
-    const int g1 = pd->pg1, mp = pd->pt - pd->pg1, nbp = pd->pnb;
-    const int ncbf = stm_upd_ncb(s, p), nslf = stm_upd_nsl(s);
-    if (ncbf <= 0) return;
-    const int c0 = pd->pc0;
-    if (nbp <= 0 || mp <= 0 || c0 >= s.fn || sl * SLAB >= mp) return;
-    const bool deferred = pd->t_deferred != 0;                     // T was left to the update by the panel kernel
-    const int nc = min(BN, s.fn - c0);
-    const long long ld = s.ld;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
     const int lrow = tid & 63, lcg = tid >> 6;
-    double *Vs = dyn_lds, *Cs = Vs + STM_NB * VS, *Ws = Cs + BN * VS;
-    if (tid < STM_NB) {
-        s_pd[tid] = (tid < nbp) ? pd->pdiag[tid] : STM_BIGROW;
-        s_tau[tid] = (tid < nbp) ? c.Tau[s.rp + pd->pk1 + tid] : 0.0;
-    }
-    const double *Vg = c.Farena + s.foff + g1 + (long long)pd->pk1 * ld;
+    FrontNum *num = &c.fnum[f];
+    // Everything that hangs on (f, p) alone in ONE memory round trip: every lane asks for one word of the front's FrontSym and one of
+    // the head of the panel's PanelDesc (pg1 .. t_deferred), every wave for itself, and the fields come out of the lanes as wave-uniform
+    // scalars; the slots of the workspaces go with them.  (Field by field -- `c.fs[f].npanels`, then the early return, then `pd->pg1`,
+    // ... -- the compiler waits for each load where the next branch needs it: seven dependent round trips, 4 us, before the tile's
+    // loads could be issued.  Agent-scope loads: one instruction each, issued here.)
+    constexpr int FSW = (int)(sizeof(FrontSym) / sizeof(int)), PDW = (int)(offsetof(PanelDesc, pad3) / sizeof(int));
+    static_assert(FSW <= 64 && PDW <= 64 && offsetof(PanelDesc, pdiag) / sizeof(int) + STM_NB <= 64, "one word per lane");
+    const int wfs = ld_agent(reinterpret_cast<const int *>(&c.fs[f]) + min(lane, FSW - 1));
+    const int wpd = ld_agent(reinterpret_cast<const int *>(&num->pd[STM_PDI(p)]) + min(lane, PDW - 1));
+    const int tsl = ld_agent(&c.tslot[f]);
+    const long long wpo = wpoff[fi];
+    // (no branch around the load: a branch is a place where the compiler waits for what is in flight; &wpoff[fi] is just a valid address)
+    const long long ypl = __hip_atomic_load(c.ypoff ? &c.ypoff[f] : &wpoff[fi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool pairf = c.ypoff && ypl >= 0;                         // a pair / quad update front
+#define B0FS(field) __builtin_amdgcn_readlane(wfs, (int)(offsetof(FrontSym, field) / sizeof(int)))
+#define B0PD(field) __builtin_amdgcn_readlane(wpd, (int)(offsetof(PanelDesc, field) / sizeof(int)))
+    FrontSym s;                                                    // (the fields this role reads)
+    s.foff = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane(wfs, (int)(offsetof(FrontSym, foff) / sizeof(int)) + 1) << 32) |
+                         (unsigned)B0FS(foff));
+    s.ld = B0FS(ld); s.fn = B0FS(fn); s.rp = B0FS(rp); s.fm_ub = B0FS(fm_ub); s.npanels = B0FS(npanels); s.tpan = B0FS(tpan);
+    const int g1 = B0PD(pg1), mp = B0PD(pt) - g1, pk1 = B0PD(pk1), nbp = B0PD(pnb), c0 = B0PD(pc0);
+    const bool deferred = B0PD(t_deferred) != 0;                   // T was left to the update by the panel kernel
+    const int pdv = __shfl(wpd, (int)(offsetof(PanelDesc, pdiag) / sizeof(int)) + (lane & (STM_NB - 1)));      // pdiag[lane & 31]
+#undef B0FS
+#undef B0PD
+    if (p >= s.npanels) return;
+    const int ncbf = stm_upd_ncb(s, p), nslf = stm_upd_nsl(s);
+    if (ncbf <= 0) return;
+    if (nbp <= 0 || mp <= 0 || c0 >= s.fn || sl * SLAB >= mp) return;
+    const int nc = min(BN, s.fn - c0);
+    const long long ld = s.ld;
+    auto img = [&](int k) { return dyn_lds + k * (BN * VS); };       // the four chunk images (the plan: above)
+    double *Ws = dyn_lds + 4 * BN * VS;
+    // (tau goes ahead of the tile's loads and into LDS behind them: a wave that waited for it here would issue its part of the tile late)
+    const double tauv = ld_agent(&c.Tau[s.rp + pk1 + min(lane & (STM_NB - 1), nbp - 1)]);
+    const double *Vg = c.Farena + s.foff + g1 + (long long)pk1 * ld;
     double *Cg = c.Farena + s.foff + g1 + (long long)c0 * ld;
-    const int r00 = sl * SLAB, rend = min(mp, (sl + 1) * SLAB);
+    const int r00 = sl * SLAB, nch = (min(mp, (sl + 1) * SLAB) - r00 + RB - 1) / RB;     // the slab's chunks: 1 .. SLAB / RB
+    const int nsl = (mp + SLAB - 1) / SLAB;
+    const int gslot = pairf ? min(ncbf, c.sweep) : ncbf;                                                 // (as in k_upd_w)
+    // (the slots as offsets, their addresses formed where they are used: two scalar registers each less to keep across the role)
+    const long long goff = wpo + ((long long)gslot * nslf) * (STM_NB * BN);
+    auto Wslot = [&] { return Wp + wpo; };                                                              // column block 0
+    auto Gslot = [&] { return Wp + goff; };
+    auto Tslot = [&] { return c.Tws + (long long)STM_TSLOT(tsl, p) * STM_NB * STM_NB; };
     UpdChunk ck[SLAB / RB];
 #pragma unroll
     for (int q = 0; q < SLAB / RB; q++) upd_chunk_load(ck[q], Vg, Cg, ld, r00 + q * RB + lrow, mp, nbp, nc, lcg);
-    const int nsl = (mp + SLAB - 1) / SLAB;
-    const int gslot = (c.ypoff && c.ypoff[f] >= 0) ? min(ncbf, c.sweep) : ncbf;                         // (as in k_upd_w)
-    double *Wslot = Wp + wpoff[fi];                                                                     // column block 0
-    double *Gslot = Wp + wpoff[fi] + ((long long)gslot * nslf) * (STM_NB * BN);
-    double *Tslot = c.Tws + (long long)STM_TSLOT(c.tslot[f], p) * STM_NB * STM_NB;
+    if (tid < STM_NB) {
+        s_pd[tid] = (tid < nbp) ? pdv : STM_BIGROW;
+        s_tau[tid] = (tid < nbp) ? tauv : 0.0;
+    }
     __syncthreads();
     B0TL(0);
     // ---- phase 1: partial W1 = V(slab)' C(slab) and, for a deferred T, partial G = V(slab)' V(slab) ----
     const int mi = wid >> 1, ni = wid & 1;
     d4 acc = {0, 0, 0, 0}, accg = {0, 0, 0, 0};
+    upd_chunk_to_lds(ck[0], r00 + lrow, mp, nbp, nc, s_pd, g1, lrow, lcg, img(0), img(1));
+    __syncthreads();
 #pragma unroll
     for (int q = 0; q < SLAB / RB; q++) {
         const int r0 = r00 + q * RB;
-        if (r0 < rend) {
-            upd_chunk_to_lds(ck[q], r0 + lrow, mp, nbp, nc, s_pd, g1, lrow, lcg, Vs, Cs);
-            __syncthreads();
+        if (q < nch) {
+            const double *Vs = img(2 * (q & 1)), *Cs = img(2 * (q & 1) + 1);
 #pragma unroll
             for (int kk = 0; kk < RB / 4; kk++) {
                 const double a = Vs[(16 * mi + l15) * VS + 4 * kk + l4];
@@ -601,14 +673,17 @@ __device__ __forceinline__ void dev_k_upd_b0(const DevCtx &c, const int *__restr
                     accg = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, accg, 0, 0, 0);
                 }
             }
+            if (q + 1 < nch)                              // (the next chunk, into the other pair)
+                upd_chunk_to_lds(ck[(q + 1) % (SLAB / RB)], r0 + RB + lrow, mp, nbp, nc, s_pd, g1, lrow, lcg, img(2 * ((q + 1) & 1)),
+                                 img(2 * ((q + 1) & 1) + 1));
             __syncthreads();
         }
     }
-    double *s_G = Vs, *s_W1 = Vs + STM_NB * WS, *s_T = Cs;         // (the chunk images are free between the phases)
+    double *s_G = img(0), *s_W1 = img(0) + STM_NB * WS, *s_T = img(1);     // (pair 0 is free between the phases)
     B0TL(1);
     bool last = true;
     if (nsl > 1) {
-        double *W = Wslot + (long long)sl * (STM_NB * BN), *G = Gslot + (long long)sl * (STM_NB * BN);
+        double *W = Wslot() + (long long)sl * (STM_NB * BN), *G = Gslot() + (long long)sl * (STM_NB * BN);
 #pragma unroll
         for (int r = 0; r < 4; r++) st_agent(&W[(16 * mi + l4 + 4 * r) * BN + 16 * ni + l15], acc[r]);
         if (deferred) {
@@ -631,9 +706,31 @@ __device__ __forceinline__ void dev_k_upd_b0(const DevCtx &c, const int *__restr
         B0TL(2);
         if (!stm_wait_ge(flag, epoch, c.abort, &s_ok)) { if (tid == 0) STM_SET_PERR(c, num); return; }
         B0TL(3);
-        for (int e = tid; e < STM_NB * BN; e += NT) {
-            s_W1[(e / BN) * WS + (e % BN)] = stm_ordered_sum<true>(Wslot + e, STM_NB * BN, nsl);        // fixed order: deterministic
-            if (deferred) s_G[(e / BN) * WS + (e % BN)] = stm_ordered_sum<true>(Gslot + e, STM_NB * BN, nsl);
+        // (fixed order: deterministic.  A thread's four entries of W1 and of G as ONE batch of ordered sums: each sum alone is a round trip)
+        constexpr int NE = STM_NB * BN / NT;
+        if (deferred) {
+            const double *pp[2 * NE];
+            double v[2 * NE];
+#pragma unroll
+            for (int k = 0; k < NE; k++) { pp[k] = Wslot() + tid + k * NT; pp[NE + k] = Gslot() + tid + k * NT; }
+            stm_ordered_sums<2 * NE, 4>(v, pp, STM_NB * BN, nsl);
+#pragma unroll
+            for (int k = 0; k < NE; k++) {
+                const int e = tid + k * NT;
+                s_W1[(e / BN) * WS + (e % BN)] = v[k];
+                s_G[(e / BN) * WS + (e % BN)] = v[NE + k];
+            }
+        } else {
+            const double *pp[NE];
+            double v[NE];
+#pragma unroll
+            for (int k = 0; k < NE; k++) pp[k] = Wslot() + tid + k * NT;
+            stm_ordered_sums<NE, 8>(v, pp, STM_NB * BN, nsl);
+#pragma unroll
+            for (int k = 0; k < NE; k++) {
+                const int e = tid + k * NT;
+                s_W1[(e / BN) * WS + (e % BN)] = v[k];
+            }
         }
     } else {
 #pragma unroll
@@ -652,17 +749,18 @@ __device__ __forceinline__ void dev_k_upd_b0(const DevCtx &c, const int *__restr
             for (int e = tid; e < STM_NB * STM_NB; e += NT) {
                 const int a = e % STM_NB, b = e / STM_NB;
                 const double tv = (a <= b && a < nbp && b < nbp) ? s_Tb[a][b] : 0.0;
-                Tslot[e] = tv;
+                Tslot()[e] = tv;
                 if (Tkeep) Tkeep[e] = tv;
             }
         }
     } else {
-        for (int e = tid; e < STM_NB * STM_NB; e += NT) s_Tb[e % STM_NB][e / STM_NB] = Tslot[e];
+        for (int e = tid; e < STM_NB * STM_NB; e += NT) s_Tb[e % STM_NB][e / STM_NB] = Tslot()[e];
         __syncthreads();
     }
     B0TL(5);
-    // W2 = T' W1 (k_upd_c's prologue)
+    // W2 = T' W1 (k_upd_c's prologue); the V image of chunk 0 goes into pair 1 beside it
     {
+        upd_chunk_v_to_lds(ck[0], r00 + lrow, mp, nbp, s_pd, g1, lrow, lcg, img(2));
         const d4 w2 = dev_w2_tile(s_T, WS, 1, s_W1, wid, lane);      // (T(q, l) = s_Tb[q][l]: zero below the diagonal and beyond nbp)
 #pragma unroll
         for (int r = 0; r < 4; r++) Ws[(16 * (wid >> 1) + l4 + 4 * r) * WS + 16 * (wid & 1) + l15] = w2[r];
@@ -670,13 +768,16 @@ __device__ __forceinline__ void dev_k_upd_b0(const DevCtx &c, const int *__restr
     __syncthreads();
     B0TL(6);
     // ---- phase 2: C(slab) -= V(slab) W2 from the registers (k_upd_c) ----
+    const int nch2 = wave_uniform(nch);                            // (its own copy: the tests of phase 1 kept as lane masks across the role spill)
 #pragma unroll
     for (int q = 0; q < SLAB / RB; q++) {
         const int r0 = r00 + q * RB;
-        if (r0 < rend) {
+        if (q < nch2) {
             const int i = r0 + lrow;
-            upd_chunk_to_lds(ck[q], i, mp, nbp, nc, s_pd, g1, lrow, lcg, Vs, Cs);
-            __syncthreads();
+            const double *Vs = img(2 * ((q + 1) & 1));
+            double *Ps = img(2 * ((q + 1) & 1) + 1);
+            if (q + 1 < nch2)
+                upd_chunk_v_to_lds(ck[(q + 1) % (SLAB / RB)], i + RB, mp, nbp, s_pd, g1, lrow, lcg, img(2 * (q & 1)));
             d4 u0 = {0, 0, 0, 0}, u1 = {0, 0, 0, 0};
 #pragma unroll
             for (int kk = 0; kk < STM_NB / 4; kk++) {
@@ -689,18 +790,17 @@ __device__ __forceinline__ void dev_k_upd_b0(const DevCtx &c, const int *__restr
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int row = 16 * wid + l4 + 4 * r;
-                Cs[l15 * VS + row] -= u0[r];
-                Cs[(16 + l15) * VS + row] -= u1[r];
+                Ps[l15 * VS + row] = u0[r];
+                Ps[(16 + l15) * VS + row] = u1[r];
             }
             __syncthreads();
             if (i < mp) {
 #pragma unroll
                 for (int qq = 0; qq < 8; qq++) {
                     const int col = lcg * 8 + qq;
-                    if (col < nc) Cg[i + col * ld] = Cs[col * VS + lrow];
+                    if (col < nc) Cg[i + col * ld] = ck[q].c[qq] - Ps[col * VS + lrow];
                 }
             }
-            __syncthreads();
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -827,6 +927,7 @@ __global__ __launch_bounds__(NT, 2) void k_upd_fw(DevCtx c, const int *__restric
 // launchers (host side calls these; no HIP types leak into the C ABI)
 // ------------------------------------------------------------------------------------------------
 int stm_update_lds_bytes(void) { return (int)((2 * BN * VS + STM_NB * WS) * sizeof(double)); }
+static size_t stm_update_b0_lds_bytes(void) { return (size_t)STM_B0_LDS_DOUBLES * sizeof(double); }      // (k_upd_b0w only: dev_k_upd_b0's plan)
 int stm_launch_update(const DevCtx &c, const int *flist, const int *plist, int nfr, int cb0, int ncb, hipStream_t st)
 {
     if (nfr <= 0 || ncb <= 0) return 0;
@@ -868,7 +969,7 @@ int stm_launch_update_fw(const DevCtx &c, const int *flist, const int *plist, in
         const int rspw = (int)knobs::once<knobs::K_RSPW_W>();
         const int uy = (maxsl + rspw - 1) / rspw;
         hipLaunchKernelGGL(k_upd_b0w, dim3(maxsl > rest ? maxsl : rest, rest > 0 ? uy : 1, rest > 0 ? 2 * nfr : nfr), dim3(NT),
-                           (size_t)stm_update_lds_bytes(), st, c, flist, plist, nfr, maxsl, rest > 0 ? rest : 0, Wp, wpoff, wcnt, wflag, epoch,
+                           stm_update_b0_lds_bytes(), st, c, flist, plist, nfr, maxsl, rest > 0 ? rest : 0, Wp, wpoff, wcnt, wflag, epoch,
                            Wp2, wcnt2, rspw);
         return (int)hipGetLastError();
     }
@@ -921,5 +1022,6 @@ int stm_configure_update(void)
 {
     CK(hipFuncSetAttribute((const void *)k_update, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
     CK(hipFuncSetAttribute((const void *)k_update_n, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    CK(hipFuncSetAttribute((const void *)k_upd_b0w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stm_update_b0_lds_bytes()));
     return 0;
 }
