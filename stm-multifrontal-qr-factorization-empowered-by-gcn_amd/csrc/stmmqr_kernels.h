@@ -57,6 +57,8 @@ struct DevCtx {
                                //  2048 column group (dbg >> 20) & 7 of every pipelined panel starts late (tests)
                                //  4096 every column group but the first gives up waiting at once (tests: recovery)
                                //  16384 no wave-pipelined panels (short panels through the multi-workgroup pipeline too)
+                               //  32768 timeline of the block-0 role (tests: how many workgroup sets ran it)
+                               //  65536 host only: one stderr line per front of every pair / quad sweep launch (tests)
 };
 
 int stm_configure_kernels(void);       // (stmmqr_panel.hip; calls the other translation units' stm_configure_*)

@@ -165,6 +165,11 @@ struct Run {
                     LCHK(stm_launch_update_split(c, act + o, pl + o, n, 0, P.sweep - r, S.maxsl_pk[r], Wp, wl + o, wcnt, 1, q));
                     nlaunch += 2;
                     if (r == P.sweep - 1) {
+                        if (c.dbg & 65536)                     // tests: the sweep launches by front, with the front's own column blocks
+                            for (int i = 0; i < n; i++)
+                                fprintf(stderr, "[sweep launch] w %d step %d front %d panel %d ncbp %d nslf %d (launch: ncbp %d maxsl %d)\n", P.sweep,
+                                        cur_step, P.lists[S.act_off + o + i], panel(S, o + i), stm_upd_ncb(front(S, o + i), panel(S, o + i)) - 1,
+                                        stm_upd_nsl(front(S, o + i)), S.maxcbp_po, S.maxsl_pk[r]);
                         if (P.sweep == 4) LCHK(stm_launch_update_quad(c, act + o, pl + o, n, S.maxcbp_po, S.maxsl_pk[r], Wp, wl + o, wcnt, q));
                         else LCHK(stm_launch_update_pair(c, act + o, pl + o, n, S.maxcbp_po, S.maxsl_pk[r], Wp, wl + o, wcnt, q));
                         nlaunch += 3;

@@ -117,6 +117,8 @@ def _testlib_symbolic(sym):
 
 @pytest.mark.parametrize("m", [700, 2600, 4500])
 def test_one_front_plan_adversarial(pkg, oracle, monkeypatch, m):
+    """At n = 160 (five panels) the quad sweep of the `quad` configuration has no column (ncbp = 0 after panel 3) and the pair
+    sweep has two column blocks once: the sweeps themselves are covered by tests/test_gpu_sweeps.py."""
     n = N_PLAN
     F0, St0, crafted = make_adversarial(m, n, "full")
     rank, _, Rdead, _ = ref_front(F0, St0, n, TOL, n)
