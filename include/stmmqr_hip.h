@@ -456,6 +456,57 @@ int stmmqr_plan_rmult(stmmqr_plan *plan, int trans, const double *X, stm_long ld
 int stmmqr_plan_condest(stmmqr_plan *plan, stm_long ncol, int kind, int iters, double *out /* [8] */, double *v /* [ncol] or NULL */,
                         int on_device);
 
+/* Minimum-norm least squares on rank-deficient factors.  Every solve above returns the BASIC solution: x = 0 on the columns whose
+ * pivot died.  With pc the r live and jd the d dead pivot columns among the first ncol (R's column order), R11 = R(:, pc) and
+ * R12 = R(:, jd):
+ *     W = R11^-1 R12,   N = [-W on pc; I on jd]  (ncol x d),   R N = 0,
+ * so |A E N(:, k)|_2 <= tol + rounding (only what the rank test dropped), and the minimum-norm least-squares solution is
+ *     x_min = (I - N G^-1 N') x_basic,   G = N'N = I + W'W = L L'   (what lsqminnorm, spqr_cod or a pseudo-inverse return).
+ * N, G and L live on the device and belong to the factorization held: the first call with a given ncol builds them (N a batch of
+ * STMMQR_RHS_BATCH dead columns per pass over the tree: a unit vector through the product with R, then the back substitution, and one
+ * step of refinement on a residual R N whose row sums are carried in two doubles, which takes the error of N from eps cond(R11) to
+ * eps (1 + eps cond(R11)^2); G by
+ * 32 x 32 tiles over row slabs of STMMQR_NULL_SLAB rows on the matrix cores; L by a right-looking blocked Cholesky factorization),
+ * later calls find them, the next factorization releases them.  While held, stmmqr_plan_device_bytes counts their
+ * 8 (ncol d + d^2 + 1024 ceil(d / 32)) + 4 d bytes.  The projector is applied twice (one pass leaves |N'x| / (|N| |x|) near
+ * |W|_2 u, the second brings it to u).  The error of x_min is governed by cond(R11) max(1, |W|_2) u, not by cond(G).
+ *   stmmqr_plan_nullspace        *ndead = d.  N non-NULL (ldn >= ncol): receives N, ncol x d column-major; column k belongs to the k-th
+ *                                dead column in R's column order: exactly 1.0 on that column, exactly 0.0 on the other dead columns,
+ *                                -W(:, k) on the live ones.  permuted == 0: the rows are in the caller's column order (scattered
+ *                                through Qfill); permuted != 0: in R's column order.  N NULL: only *ndead is written, nothing is built.
+ *   stmmqr_plan_project_minnorm  X (ncol x nrhs, ldx >= ncol, in place) <- (I - N G^-1 N')^2 X; permuted as above.  info ([8], host,
+ *                                may be NULL): [0] d; [1] the largest |N'x_out|_2 / (|N|_F |x_in|_2) over the right-hand sides, measured
+ *                                on the device after the second pass (0 where x_in = 0); [2] |N|_F; [3] the smallest diagonal entry
+ *                                of L (>= 1 in exact arithmetic); [4] 1 if this call built N and L, 0 if it found them; [5..7] 0.
+ *   stmmqr_plan_solve_lsminnorm  stmmqr_plan_solve followed by the projector: B m x nrhs, X n x nrhs.  Needs H (keepH = 0: refused with
+ *                                stmmqr_plan_solve's message); the other two read R only and work on plans with and without H.
+ * ncol < the columns of the plan: the plan holds [A B] as stmmqr_plan_solve_carried expects it (the same messages) and the trailing
+ * columns take no part.  d = 0: *ndead = 0, X comes back bit for bit, nothing is launched and nothing is allocated.  nrhs = 0 returns
+ * 0 and writes nothing.  on_device: N, X and B are device pointers.
+ * Deterministic: no atomics, every sum in an order fixed by (ncol, d, the slab height) alone, so column j of a batch carries the bits
+ * of the one-vector call, host and device output, two calls, and plans with and without H carry the same bits.
+ * STMMQR_ERR_INVALID (the message says why; the plan stays usable): null plan or nothing factorized, bad pointers or leading
+ * dimensions, ncol out of range, the carried conditions not met for ncol < n, a plan that does not hold the whole tree, or a pivot
+ * of the Cholesky factorization that is not positive and finite (only a non-finite W can do that; the message names the pivot).
+ * STMMQR_ERR_OUT_OF_MEMORY: no room for N, G and the partial sums; whatever was allocated is released and the plan stays usable.
+ * Measured on an MI355X, largest ratio to the bounds of tests/test_gpu_nullspace.py over the committed fixtures:
+ * |R N(:, k)| 1.4e-3 of its bound, |A E N(:, k)| 0.81 of tol + that bound (reorientation_8), |N - N_ref| / |N_ref| <= 1.8e-15, and
+ * 1.3e-12 on lns_3937 (cond(R11) 8.3e12; 1e-8 without the refinement step); after the second pass |N'x| / (|N|_F |x|) <= 3.3e-17
+ * against the device's own N and 3.5e-3 of 8 (d + 2) eps at most against the long double N_ref.  Whole path against a dense SVD
+ * solution: 2.3e-15 (small fixtures), 2.3e-12 (dwt_992).
+ * Times: cvxqp3 (n = 17500, d = 458) N 418 ms, Gram 0.43 ms, Cholesky 0.55 ms, one projection 1.24 ms (32 vectors: 1.50 ms) next to
+ * 8.8 ms of one stmmqr_plan_solve; lns_3937 (n = 3908, d = 2086) 222 / 0.87 / 2.87 ms, 7.9 ms (8.4 ms), solve 3.0 ms.
+ * Out of scope: a stmmqr_sparseqr_* entry point.  The singleton block R1 of that object lives on the host and is no part of the
+ * plan (as for the variances); the stmmqr_ls object below removes no singletons and is the home of this feature. */
+int stmmqr_plan_nullspace(stmmqr_plan *plan, stm_long ncol, stm_long *ndead, double *N, stm_long ldn, int permuted, int on_device);
+int stmmqr_plan_project_minnorm(stmmqr_plan *plan, stm_long ncol, double *X, stm_long ldx, stm_long nrhs, int permuted, int on_device,
+                                double *info /* [8] or NULL, host */);
+int stmmqr_plan_solve_lsminnorm(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int on_device,
+                                double *info);
+/* ms [3]: device milliseconds of the last build of the basis the plan holds -- N, the Gram matrix, the Cholesky factorization
+ * (STMMQR_ERR_INVALID if it holds none). */
+int stmmqr_plan_nullspace_times(const stmmqr_plan *plan, double *ms);
+
 /* Least squares with the right-hand sides carried through the factorization: the plan holds a factorization of the m x (n + nrhs)
  * matrix [A B] made with ntol = n (the columns of B are never rank-tested), whose Qfill is the identity on the last nrhs columns.
  * The reflectors reached B as trailing columns, so C = Q'B sits in the last nrhs columns of R and no Q is needed:
@@ -721,6 +772,11 @@ int stmmqr_ls_covariance_entries(stmmqr_ls *ls, stm_long npairs, const stm_long 
 /* after a solve: stmmqr_plan_condest with ncol = n of A -- the condition of A(:, live), which says how far the solution, the variances
  * and the leverages above can be trusted (out [8], v [n] or NULL).  Refuses as stmmqr_ls_covariance_diag does. */
 int stmmqr_ls_condest(stmmqr_ls *ls, int kind, int iters, double *out, double *v, int on_device);
+/* after a solve: stmmqr_plan_nullspace / stmmqr_plan_project_minnorm with ncol = n of A, in A's column order: the null vectors of A
+ * as the rank test saw it, and the minimum-norm solution from the basic one that stmmqr_ls_solve returns (X n x nrhs, in place; the
+ * residuals do not change).  They refuse as stmmqr_ls_covariance_diag does. */
+int stmmqr_ls_nullspace(stmmqr_ls *ls, stm_long *ndead, double *N, stm_long ldn, int on_device);
+int stmmqr_ls_project_minnorm(stmmqr_ls *ls, double *X, stm_long ldx, stm_long nrhs, int on_device, double *info);
 void stmmqr_ls_free(stmmqr_ls *ls);
 
 void stmmqr_shutdown(void);                           /* optional end-of-use call for dlopen()ing hosts: device sync  */

@@ -156,6 +156,10 @@ lib.stmmqr_plan_covariance_diag.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.
 lib.stmmqr_plan_rmult.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int]
 lib.stmmqr_plan_condest.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_plan_leverage.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int]
+lib.stmmqr_plan_nullspace.argtypes = [C.c_void_p, C.c_long, c_long_p, C.c_void_p, C.c_long, C.c_int, C.c_int]
+lib.stmmqr_plan_project_minnorm.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, c_double_p]
+lib.stmmqr_plan_nullspace_times.argtypes = [C.c_void_p, c_double_p]
+lib.stmmqr_plan_solve_lsminnorm.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, c_double_p]
 lib.stmmqr_plan_covariance_entries.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_set_keep_h.argtypes = [C.c_void_p, C.c_int]
 lib.stmmqr_sparseqr_solve_seminormal.argtypes = [C.c_void_p, c_long_p, c_long_p, c_double_p, c_double_p, C.c_long, C.c_long, c_double_p,
@@ -310,6 +314,29 @@ class QRNumeric:
         self.rh_total = rh_total
         self.rank = self.rank1 = self.maxfrank = self.maxfm = 0
         self.stats = {}
+
+
+def _nullspace_array(call, what, ncol):
+    """call(ndead, N, ldn) of a nullspace entry point with host arrays -> the ncol x d array (the count first, then the basis)"""
+    nd = C.c_long(0)
+    _check(call(C.byref(nd), None, max(ncol, 1)), what)
+    N = np.zeros((max(ncol, 0), int(nd.value)), order="F")
+    if N.size:
+        _check(call(C.byref(nd), N.ctypes.data, max(ncol, 1)), what)
+    return N
+
+
+def _minnorm_info(v):
+    return {"d": int(v[0]), "orth": float(v[1]), "norm_N": float(v[2]), "min_diag_L": float(v[3]), "built": bool(v[4])}
+
+
+def _project(call, what, X, rows, with_info):
+    """call(X, ldx, nrhs, info) of a projector entry point on a copy of X (rows or rows x nrhs)"""
+    Xf = np.array(X, dtype=np.float64, order="F", copy=True).reshape(rows, -1, order="F")
+    info = np.zeros(8)
+    _check(call(Xf.ctypes.data, max(rows, 1), Xf.shape[1], _dp(info)), what)
+    out = Xf[:, 0] if np.ndim(X) == 1 else Xf
+    return (out, _minnorm_info(info)) if with_info else out
 
 
 def _condest_dict(call, what, ncol, with_vector):
@@ -625,6 +652,41 @@ class HipQR:
         return _condest_dict(lambda out, v: lib.stmmqr_plan_condest(self._h, self.sym["n"] if ncol is None else int(ncol), int(kind), int(iters),
                                                                     out, v, 0),
                              "stmmqr_plan_condest", self.sym["n"] if ncol is None else int(ncol), with_vector)
+
+    def nullspace(self, ncol=None, permuted: bool = False) -> np.ndarray:
+        """The null-space basis N (ncol x d) of R over its first ncol columns (stmmqr_plan_nullspace): column k belongs to the k-th dead
+        pivot column in R's column order, is exactly 1 there, exactly 0 on the other dead columns and -R11^-1 R12(:, k) on the live
+        ones, so R N = 0 and |A E N(:, k)| <= tol + rounding.  Rows in the caller's column order (permuted: in R's).  ncol as in
+        covariance_diag.  Reads R only."""
+        ncol = self.sym["n"] if ncol is None else int(ncol)
+        return _nullspace_array(lambda nd, N, ld: lib.stmmqr_plan_nullspace(self._h, ncol, nd, N, ld, int(bool(permuted)), 0),
+                                "stmmqr_plan_nullspace", ncol)
+
+    def nullspace_times(self) -> dict:
+        """device ms of the last build of the basis held: {"N", "gram", "cholesky"} (stmmqr_plan_nullspace_times)"""
+        v = np.zeros(3)
+        _check(lib.stmmqr_plan_nullspace_times(self._h, _dp(v)), "stmmqr_plan_nullspace_times")
+        return {"N": float(v[0]), "gram": float(v[1]), "cholesky": float(v[2])}
+
+    def project_minnorm(self, X: np.ndarray, ncol=None, permuted: bool = False, with_info: bool = False):
+        """(I - N G^-1 N')^2 X for X of ncol rows (a vector or ncol x nrhs), G = N'N: the component of X in the null space of R is
+        removed, which turns the basic least-squares solution into the minimum-norm one (stmmqr_plan_project_minnorm).  Returns a new
+        array; with_info also {"d", "orth": the largest |N'x_out| / (|N|_F |x_in|), "norm_N", "min_diag_L", "built"}."""
+        ncol = self.sym["n"] if ncol is None else int(ncol)
+        return _project(lambda Xp, ld, k, info: lib.stmmqr_plan_project_minnorm(self._h, ncol, Xp, ld, k, int(bool(permuted)), 0, info),
+                        "stmmqr_plan_project_minnorm", X, ncol, with_info)
+
+    def solve_lsminnorm(self, B: np.ndarray, with_info: bool = False):
+        """The minimum-norm least-squares solution of min |A x - b| for B of m rows: solve() followed by the projector
+        (stmmqr_plan_solve_lsminnorm).  Needs H.  with_info as project_minnorm."""
+        m, n = self.sym["m"], self.sym["n"]
+        Bf = np.array(B, dtype=np.float64, order="F", copy=True).reshape(m, -1, order="F")
+        X = np.zeros((n, Bf.shape[1]), order="F")
+        info = np.zeros(8)
+        _check(lib.stmmqr_plan_solve_lsminnorm(self._h, Bf.ctypes.data, max(m, 1), X.ctypes.data, max(n, 1), Bf.shape[1], 0, _dp(info)),
+               "stmmqr_plan_solve_lsminnorm")
+        out = X[:, 0] if np.ndim(B) == 1 else X
+        return (out, _minnorm_info(info)) if with_info else out
 
     def solve_carried(self, nrhs: int):
         """Least squares with the right-hand sides carried through the factorization: the plan holds [A B] factorized with
@@ -1100,6 +1162,8 @@ lib.stmmqr_ls_covariance_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_ls_leverage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_ls_covariance_entries.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
 lib.stmmqr_ls_condest.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+lib.stmmqr_ls_nullspace.argtypes = [C.c_void_p, c_long_p, C.c_void_p, C.c_long, C.c_int]
+lib.stmmqr_ls_project_minnorm.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int, c_double_p]
 lib.stmmqr_ls_free.restype = None
 lib.stmmqr_ls_free.argtypes = [C.c_void_p]
 
@@ -1196,6 +1260,17 @@ class LeastSquares:
         """after solve(): the condition of A(:, live) from the R the object holds (stmmqr_ls_condest; HipQR.condest with ncol = n)"""
         return _condest_dict(lambda out, v: lib.stmmqr_ls_condest(self._h, int(kind), int(iters), out, v, 0), "stmmqr_ls_condest", self.n,
                              with_vector)
+
+    def nullspace(self) -> np.ndarray:
+        """after solve(): the null vectors of A as the rank test saw it, n x d in A's column order (stmmqr_ls_nullspace; HipQR.nullspace
+        with ncol = n)"""
+        return _nullspace_array(lambda nd, N, ld: lib.stmmqr_ls_nullspace(self._h, nd, N, ld, 0), "stmmqr_ls_nullspace", self.n)
+
+    def project_minnorm(self, X, with_info: bool = False):
+        """after solve(): the minimum-norm solution from the basic one that solve() returns (X of n rows; stmmqr_ls_project_minnorm).
+        The residuals do not change."""
+        return _project(lambda Xp, ld, k, info: lib.stmmqr_ls_project_minnorm(self._h, Xp, ld, k, 0, info), "stmmqr_ls_project_minnorm",
+                        X, self.n, with_info)
 
     def diagnostics(self):
         """after solve(): (leverages, variances) from ONE selected inversion (stmmqr_ls_leverage): the leverages of the m rows of A

@@ -196,6 +196,11 @@ struct QbDesc {
 #define STM_SI_NB 32         // block rows of the back substitution [G | S] = R11^-1 [I | R12] and columns of a workgroup's strip
 #define STM_SI_TILE 64       // output tile of a workgroup of the product kernel (Z_PN, Z_PP)
 #define STM_SI_KC 16         // ... columns of the operands per pass through LDS
+// Null-space basis of R and the minimum-norm projector (stmmqr_nullspace.hip): tiles of the Gram matrix N'N, columns of a Cholesky
+// panel and block rows of the substitutions with L; right-hand sides of a batch that a workgroup of N'X / X -= N z carries.  The
+// height of a row slab of N is a knob (STMMQR_NULL_SLAB); tests/test_gpu_nullspace.py sits on both sides of each.
+#define STM_NULL_NB 32
+#define STM_NULL_RV 8
 // one front of the VIEW the recurrence walks (all columns of the plan, or the A part of a plan that holds [A B])
 struct SiDesc {
     long long zoff;          // the front's block of Z in the arena: (rmax + cn)^2 doubles, ld = rmax + cn, live pivots first

@@ -171,6 +171,9 @@ int stm_launch_rtsolve_big(const DevCtx &c, const RtDesc *rd, int nq, int max_st
 // then, once for all levels, z[j] = its slots in slot order (cp / slot: the transpose of Rj)
 int stm_launch_rmult(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *Rj, const int *rowbase, const double *X, double *Y,
                      hipStream_t st, int nb, const RhsBatch &B);
+// ... the same product with every row's sum carried in two doubles (k_rmult_dd: the residual of the null-space basis' refinement)
+int stm_launch_rmult_dd(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *Rj, const int *rowbase, const double *X, double *Y,
+                        hipStream_t st, int nb, const RhsBatch &B);
 int stm_launch_rtmult_dots(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *rowbase, const double *Y, double *U, int absval,
                            hipStream_t st, int nb, const RhsBatch &B);
 int stm_launch_rtmult_gather(const int *cp, const int *slot, const double *U, double *Z, int n, hipStream_t st, int nb, long long su, long long sz);
@@ -178,6 +181,28 @@ int stm_launch_rtmult_gather(const int *cp, const int *slot, const double *U, do
 int stm_launch_ce_reduce(int what, const double *a, const int *idx, const double *b, int r, double *out, hipStream_t st);
 int stm_launch_ce_map(int what, double *a, const int *idx, double *dst, int r, double d, hipStream_t st);
 int stm_launch_ce_vector(const double *x, const int *qfill, double *out, int ncol, double d, hipStream_t st);
+// null-space basis of R and the minimum-norm projector (stmmqr_nullspace.hip).  N is ncol x d (ld = ncol, R's column order), G = N'N
+// and its Cholesky factor L are d x d (ld = d): the blocks below the diagonal in place, the 32 x 32 diagonal blocks of L in Ld (1024
+// doubles each, the identity beyond d).  Every offset into N, G and the partial sums is 64-bit.
+//   unit / scatter     a batch of unit vectors e_jd[k0 + v] (X zeroed by the caller); column k0 + v of N = e - (R \ (R e)) of that batch
+//   refine             N(live rows, k0 + v) -= x of vector v, x = R \ (R N(:, k0 + v)) with the residual's row sums in two doubles
+//   gram               lower 32 x 32 tiles of N'N per row slab into Pt ([tile][slab][1024]), then their sum in slab order into G
+//   chol_panel / _update   panel p of the right-looking factorization (columns 32 p ..): nblk = block rows at or below the diagonal
+//   nt                 T (d x nb) = N'X by slab partial sums (Pt: [vector][slab][d]) added in slab order
+//   llt                T <- (L L')^-1 T, a workgroup per vector
+//   sub                X -= N T, a row per thread
+//   norm2              out[v] = |A(:, v)|_2^2
+int stm_launch_null_unit(const int *jd, int k0, int nb, double *X, long long ldx, hipStream_t st);
+int stm_launch_null_scatter(const double *Xs, long long sx, const char *Rdead, const int *jd, int k0, int nb, int ncol, double *N, hipStream_t st);
+int stm_launch_null_refine(const double *Xs, long long sx, const char *Rdead, int k0, int nb, int ncol, double *N, hipStream_t st);
+int stm_launch_null_gram(const double *N, int ncol, int d, int slab, int nslab, double *Pt, double *G, hipStream_t st);
+int stm_launch_null_chol_panel(double *G, double *Ld, int d, int p, int *err, hipStream_t st);
+int stm_launch_null_chol_update(double *G, int d, int p, hipStream_t st);
+int stm_launch_null_nt(const double *N, int ncol, int d, int slab, int nslab, const double *X, long long ldx, int nb, double *Pt, double *T,
+                       hipStream_t st);
+int stm_launch_null_llt(const double *L, const double *Ld, int d, double *T, int nb, hipStream_t st);
+int stm_launch_null_sub(const double *N, int ncol, int d, const double *T, int nb, double *X, long long ldx, hipStream_t st);
+int stm_launch_null_norm2(const double *A, long long lda, int n, int nb, double *out, hipStream_t st);
 int stm_launch_panel_msg(void *const homes[6], const long long offs[6], const long long bytes[6], void *buf, int out, hipStream_t st);
 // subtree exchange: contribution blocks between plans as fixed-size messages, packed / unpacked on the device (stmmqr_pack.hip)
 struct StmFrontMsg { long long off, slot; int f, pad; };      // front f at buf + off: [8 | slot | fn - fp] doubles

@@ -70,6 +70,7 @@ enum When { PROCESS, PLAN, SCHED, RUN, CALL };
     X(QT4, qt4, bool, FLAG, PLAIN, CALL, 1, "grouped split Q-apply (0: the per-panel launches)")                                    \
     X(LIVE_PANELS, live_panels, bool, FLAG, PLAIN, CALL, 1, "Q-apply / back substitution visit only the panels that can hold a reflector") \
     X(RESIDENT_CACHE, resident_cache, int, INT, BOOLEAN, CALL, -1, "recycled slabs: the scratch holds every front in front form (1) or one tree level (0); unset: by free memory") \
+    X(NULL_SLAB, null_slab, long, INT, MIN1, CALL, 2048, "rows of the null-space basis N per slab of the Gram matrix N'N and of N'X: a workgroup per (tile, slab), the partial sums added in slab order (read when N is built and at every projection)") \
     X(CHUNK, chunk, int, INT, PLAIN, CALL, 1, "fronts per panel launch with STMMQR_DBG bit 9")                                      \
     X(PLAN_CACHE, plan_cache, int, INT, MIN0, CALL, 1, "plans the drop-in seam keeps (0: no cache)")                                \
     X(SEAM_EARLY_ALLOC, seam_early_alloc, int, INT, PLAIN, CALL, 1, "the seam populates the returned stack beside the factorization: 0 never, 1 for cached plans, 2 for first calls too") \

@@ -235,6 +235,18 @@ int stmmqr_ls_condest(stmmqr_ls *ls, int kind, int iters, double *out, double *v
     return stmmqr_plan_condest(ls->plan, ls->n, kind, iters, out, v, on_device);
 }
 
+// the null vectors of A(:, Q) from the R of [A B] the object holds, and the projector that makes the last solve's x the minimum-norm one
+int stmmqr_ls_nullspace(stmmqr_ls *ls, stm_long *ndead, double *N, stm_long ldn, int on_device)
+{
+    if (int e = ls_fit_ready(ls, "stmmqr_ls_nullspace")) return e;
+    return stmmqr_plan_nullspace(ls->plan, ls->n, ndead, N, ldn, 0, on_device);
+}
+int stmmqr_ls_project_minnorm(stmmqr_ls *ls, double *X, stm_long ldx, stm_long nrhs, int on_device, double *info)
+{
+    if (int e = ls_fit_ready(ls, "stmmqr_ls_project_minnorm")) return e;
+    return stmmqr_plan_project_minnorm(ls->plan, ls->n, X, ldx, nrhs, 0, on_device, info);
+}
+
 void stmmqr_ls_free(stmmqr_ls *ls) { delete ls; }
 
 }  // extern "C"

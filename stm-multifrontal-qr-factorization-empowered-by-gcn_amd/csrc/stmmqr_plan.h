@@ -236,7 +236,7 @@ struct stmmqr_plan {
     stmmqr_stats stats = {};
 
     // device memory held right now: the buffers of the factorization and the index of A; of the resident-factor operations only the
-    // recycling scratch and the carried solve's view.  Their maps, work vectors, staging and T4 buffers (the rest of `res`) are not
+    // recycling scratch, the carried solve's view and the null-space basis with its Cholesky factor.  Their maps, work vectors, staging and T4 buffers (the rest of `res`) are not
     // counted: stats.device_bytes reports this number, the footprint of the factorization
     double device_bytes() const
     {
@@ -249,6 +249,7 @@ struct stmmqr_plan {
         add(d_rhtop); add(d_fin); add(d_kept); add(res.sched.d_scr); add(d_bounce); add(res.sched.d_fs_scr);
         add(a_idx.cp); add(a_idx.ci); add(a_idx.rp); add(a_idx.rj); add(a_idx.rq);
         add(res.call.d_fs_car); add(res.call.d_fnum_car); add(res.call.d_carlist); add(res.call.d_carN);
+        add(res.fact.null.d_N); add(res.fact.null.d_L); add(res.fact.null.d_Ld); add(res.fact.null.d_jd);
         return b;
     }
     DevCtx ctx() const { return ctx((int)knobs::num(knobs::K_DBG)); }

@@ -1,7 +1,8 @@
 // stmmqr_resident.h -- the state of the operations on the resident factors (stmmqr_plan::res), sorted by how long it lives, and what
-// their four host units share (included by stmmqr_plan.h, after DevBuf):
+// their five host units share (included by stmmqr_plan.h, after DevBuf):
 //   stmmqr_rfactor.cpp     the front form, the row map, the passes over the tree; qmult, rsolve, solve, solve_minnorm, solve_carried
 //   stmmqr_rcond.cpp       products with R and R', the condition estimate
+//   stmmqr_rnull.cpp       the null-space basis of R, its Gram matrix and Cholesky factor, the minimum-norm projector
 //   stmmqr_rcov.cpp        the selected inverse: variances, leverages, covariance entries
 //   stmmqr_seminormal.cpp  products with A, the seminormal solves, the minimum-norm forwarder of the SparseQR object
 #pragma once
@@ -45,6 +46,18 @@ struct ResidentState {
                                                         //  only the level at hand is in front form)
         restab::LiveCounts live;
         DevBuf<int> d_Wmap, d_rowbase;                  // restab::row_map
+        // the null-space basis of the first `ncol` columns (stmmqr_rnull.cpp): built by the first call that asks for it, found by the
+        // later ones with the same ncol; its memory goes back with the factorization
+        struct NullSpace {
+            bool ready = false;
+            long ncol = -1;
+            int d = 0, r = 0;                           // dead / live pivot columns among the first ncol
+            double nfro = 0.0, lmin = 0.0;              // |N|_F, the smallest diagonal entry of L
+            double ms[3] = {0.0, 0.0, 0.0};             // device ms of the build: N, the Gram matrix, the Cholesky factorization
+            DevBuf<double> d_N, d_L, d_Ld;              // N (ncol x d), L (d x d: the blocks below the diagonal), its 32 x 32 diagonal blocks
+            DevBuf<int> d_jd;                           // the dead columns
+            void release() { ready = false; ncol = -1; d = r = 0; d_N.release(); d_L.release(); d_Ld.release(); d_jd.release(); }
+        } null;
     } fact;
     // ---- per call: grown on demand, never shrunk
     struct Call {
@@ -61,14 +74,16 @@ struct ResidentState {
         DevBuf<FrontNum> d_fnum_car;
         DevBuf<int> d_carlist;
         DevBuf<double> d_carN;
+        DevBuf<double> d_nlX, d_nlT, d_nlP, d_nlS;     // the projector's: a batch in R's column order, N'X, its slab partial sums, norms
     } call;
-    void new_factorization() { fact.rowmap_ready = fact.scr_valid = fact.t4_valid = false; }
+    void new_factorization() { fact.rowmap_ready = fact.scr_valid = fact.t4_valid = false; fact.null.release(); }
 };
 
 // ---- what stmmqr_rfactor.cpp gives the other three units ----
 struct stmmqr_plan;
 // how every entry point starts and ends: the refusal before it looks at its other arguments; the plan's device and the maps of the
-// factorization held; the check of the kernels' error word (1 from a front's live pivot count, 2 from a lookup of k_si_leverage)
+// factorization held; the check of the kernels' error word (1 from a front's live pivot count, 2 from a lookup of k_si_leverage,
+// 3 + 4 (column + 1) from a pivot of k_null_chol_panel)
 int check_factored(const stmmqr_plan *plan);
 int begin_resident_op(stmmqr_plan &P);
 int end_resident_op(stmmqr_plan &P);
@@ -78,6 +93,8 @@ DevCtx res_ctx(stmmqr_plan &P);                                 // the fronts th
 std::vector<FrontSym> resident_front_syms(const stmmqr_plan &P);
 int level_to_front_form(stmmqr_plan &P, size_t l);
 int rhs_batch_max();
+// stmmqr_plan_solve with B and X on the host or, on_device, on the device
+int plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int on_device);
 int for_each_batch(stmmqr_plan &P, stm_long nrhs, const std::function<int(stm_long, int)> &op);
 // staging: rows x cols doubles between a caller's array (leading dimension ld; host, or device with on_device) and a device buffer that
 // holds the columns one after the other (grown if needed); stage_out waits for the stream
@@ -96,5 +113,5 @@ int r_vectors(stmmqr_plan &P, const double *Y, double *X, int nb, bool through_q
 int rt_vectors(stmmqr_plan &P, const double *Z, double *Y, int nb, bool through_qfill);
 int ensure_rmult(stmmqr_plan &P);
 int ensure_rtmult(stmmqr_plan &P);
-int rmult_pass(stmmqr_plan &P, const double *X, double *Y, int nb);
+int rmult_pass(stmmqr_plan &P, const double *X, double *Y, int nb, int twofold = 0);    // twofold: row sums carried in two doubles
 int rtmult_pass(stmmqr_plan &P, const double *Y, double *Z, int nb, int absval = 0);

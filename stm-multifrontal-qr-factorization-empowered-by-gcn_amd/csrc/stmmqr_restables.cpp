@@ -217,4 +217,19 @@ int resolve_pairs(const std::vector<FrontSym> &fs, const std::vector<long> &Supe
     }
     return 0;
 }
+
+void null_split(const std::vector<char> &rd, std::vector<int> &pc, std::vector<int> &jd)
+{
+    pc.clear(); jd.clear();
+    for (size_t j = 0; j < rd.size(); j++) (rd[j] ? jd : pc).push_back((int)j);
+}
+NullSlabs null_slabs(long ncol, long want)
+{
+    long h = std::max(1L, want);
+    while ((ncol + h - 1) / h > 65535) h *= 2;
+    return {(int)h, (int)std::max(1L, (ncol + h - 1) / h)};
+}
+int null_panels(int d) { return (d + STM_NULL_NB - 1) / STM_NULL_NB; }
+int null_panel_width(int d, int p) { return std::max(0, std::min(STM_NULL_NB, d - p * STM_NULL_NB)); }
+long long null_lower_tiles(int d) { const long long t = null_panels(d); return t * (t + 1) / 2; }
 }  // namespace restab

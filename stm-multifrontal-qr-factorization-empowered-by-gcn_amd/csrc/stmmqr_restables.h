@@ -74,4 +74,15 @@ std::vector<int> column_fronts(const std::vector<long> &Super, long nf, long nco
 // of the later one).  Returns 0, or the error code with the text for the caller's `fail`
 int resolve_pairs(const std::vector<FrontSym> &fs, const std::vector<long> &Super, const std::vector<long> &Rj, const long *Qfill, long ncol,
                   long npairs, const long *I, const long *J, std::vector<int> &trip, std::string &msg);
+
+// The null-space basis of R (stmmqr_rnull.cpp).  The live (pc) and the dead (jd) pivot columns among the first rd.size(), in R's column
+// order; the row slabs of N -- rows [s h, min(ncol, (s + 1) h)), h = the height asked for, at least 1 and doubled until a launch's
+// grid can count the slabs --; the panels of the Cholesky factorization = block rows of the substitutions (32 columns each, the last
+// one d - 32 (panels - 1) wide) and the lower tiles of the Gram matrix
+void null_split(const std::vector<char> &rd, std::vector<int> &pc, std::vector<int> &jd);
+struct NullSlabs { int height, count; };
+NullSlabs null_slabs(long ncol, long want);
+int null_panels(int d);
+int null_panel_width(int d, int p);
+long long null_lower_tiles(int d);
 }  // namespace restab

@@ -235,6 +235,8 @@ int end_resident_op(stmmqr_plan &P)
     int e = 0;
     HIPCHK(hipMemcpyAsync(&e, P.res.call.d_err.p, sizeof(int), hipMemcpyDeviceToHost, P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));
+    if ((e & 3) == 3)
+        return fail(STMMQR_ERR_INVALID, "nullspace: pivot " + std::to_string((e >> 2) - 1) + " of the Cholesky factorization of N'N is not positive and finite (R has non-finite entries)");
     if (e == 2) return fail(STMMQR_ERR_INVALID, "internal: two columns of one row of A are not in one block of the selected inverse");
     if (e) return fail(STMMQR_ERR_INVALID, "internal: live pivot count of a front differs from its rank");
     return 0;
@@ -481,7 +483,7 @@ int ensure_rtmult(stmmqr_plan &P)
     return 0;
 }
 // nb vectors X (device, R's column order, stride n) -> Y (device, R's row order, stride m) = R X; rows beyond the rank are zero
-int rmult_pass(stmmqr_plan &P, const double *X, double *Y, int nb)
+int rmult_pass(stmmqr_plan &P, const double *X, double *Y, int nb, int twofold)
 {
     const auto &S = P.res.sched;
     const RhsBatch B = rhs_strides(P);
@@ -490,7 +492,8 @@ int rmult_pass(stmmqr_plan &P, const double *X, double *Y, int nb)
     HIPCHK(hipMemsetAsync(Y, 0, (size_t)nb * (size_t)std::max(1L, P.m) * sizeof(double), P.stream));
     for (size_t l = 0; l < LV.size(); l++) {
         LCHK(level_to_front_form(P, l));
-        LCHK(stm_launch_rmult(c, P.d_lists.p + LV[l].all_off, LV[l].n_all, S.rm_rslab[l], S.d_Rj.p, P.res.fact.d_rowbase.p, X, Y, P.stream, nb, B));
+        if (twofold) LCHK(stm_launch_rmult_dd(c, P.d_lists.p + LV[l].all_off, LV[l].n_all, S.rm_rslab[l], S.d_Rj.p, P.res.fact.d_rowbase.p, X, Y, P.stream, nb, B));
+        else LCHK(stm_launch_rmult(c, P.d_lists.p + LV[l].all_off, LV[l].n_all, S.rm_rslab[l], S.d_Rj.p, P.res.fact.d_rowbase.p, X, Y, P.stream, nb, B));
     }
     return 0;
 }
@@ -575,6 +578,10 @@ int stmmqr_plan_rsolve(stmmqr_plan *plan, int system, const double *B, stm_long 
 // dead columns get x = 0 (basic solution).
 int stmmqr_plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs)
 {
+    return plan_solve(plan, B, ldb, X, ldx, nrhs, 0);
+}
+int plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *X, stm_long ldx, stm_long nrhs, int on_device)
+{
     PASS(check_factored(plan));
     if (!B || !X || ldb < plan->m || ldx < plan->n || nrhs < 0) return fail(STMMQR_ERR_INVALID, "bad solve arguments");
     if (!plan->keep_h)
@@ -586,7 +593,7 @@ int stmmqr_plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *
     const long m = P.m, n = P.n;
     if (nrhs == 0) return 0;
     HIPCHK(hipMemsetAsync(K.d_err.p, 0, sizeof(int), P.stream));
-    PASS(stage_in(K.d_Xall, B, ldb, m, nrhs, 0, st));
+    PASS(stage_in(K.d_Xall, B, ldb, m, nrhs, on_device, st));
     LCHK(grow(K.d_Yall, (size_t)(n * nrhs)));
     PASS(for_each_batch(P, nrhs, [&](stm_long j, int nb) -> int {
         LCHK(stm_launch_perm(K.d_Xall.p + j * m, P.res.sched.d_PLinv.p, K.d_W.p, (int)m, 1, st, nb, m, m));
@@ -595,7 +602,7 @@ int stmmqr_plan_solve(stmmqr_plan *plan, const double *B, stm_long ldb, double *
         LCHK(stm_launch_perm(K.d_Xs.p, P.has_qfill ? P.res.sched.d_Qfill.p : nullptr, K.d_Yall.p + j * n, (int)n, 1, st, nb, n, n));   // X[Qfill[j]] = x[j]
         return 0;
     }));
-    PASS(stage_out(K.d_Yall, X, ldx, n, nrhs, 0, st));
+    PASS(stage_out(K.d_Yall, X, ldx, n, nrhs, on_device, st));
     return end_resident_op(P);
 }
 

@@ -96,6 +96,68 @@ __global__ __launch_bounds__(RM_NT) void k_rmult(DevCtx c, const int *__restrict
     }
 }
 
+// Y = R X with every row's sum carried in two doubles (a product's rounding error by fma, the sums by the error-free two-sum;
+// contraction is switched off there): the result is the rounded EXACT row sum up to eps^2 sum |r_ik x_k|, which
+// is what the refinement of the null-space basis needs of a residual that cancels to eps cond(R) of its terms.  k_rmult<1>'s rows, column
+// order and masks; vector blockIdx.z of a batch.
+__device__ __forceinline__ void dd_add_product(double v, double x, double &hi, double &lo)
+{
+#pragma clang fp contract(off)    // (p must stay a rounded product: fused into the sums below, its error e would be counted twice)
+    const double p = v * x, e = __builtin_fma(v, x, -p);
+    const double s = hi + p, bb = s - hi;
+    const double err = (hi - (s - bb)) + (p - bb);
+    hi = s;
+    lo = lo + (err + e);
+}
+__global__ __launch_bounds__(RM_NT) void k_rmult_dd(DevCtx c, const int *__restrict__ flist, const int *__restrict__ Rj,
+                                                    const int *__restrict__ rowbase, const double *X, double *Y, RhsBatch B)
+{
+    X += (long long)blockIdx.z * B.x; Y += (long long)blockIdx.z * B.w;
+    __shared__ int s_scan[NW];
+    __shared__ int s_lc[RM_ROWS];
+    __shared__ double s_x[RM_XC];
+    const int f = flist[blockIdx.x];
+    const FrontSym s = c.fs[f];
+    const int fp = s.fp, fn = s.fn, fm = c.fnum[f].fm;
+    const int i0 = (int)blockIdx.y * RM_ROWS, tid = threadIdx.x;
+    if (fp <= 0 || i0 >= min(fp, fm)) return;           // (uniform: no row of R in this slab)
+    const int *St = c.Stair + s.rp;
+    int rm;
+    {
+        const int per = (fp + RM_NT - 1) / RM_NT;
+        const int k0 = min(fp, tid * per), k1 = min(fp, k0 + per);
+        int cnt = 0;
+        for (int k = k0; k < k1; k++) cnt += (St[k] != 0);
+        int total;
+        const int incl = block_incl_scan(cnt, s_scan, &total);
+        int q = incl - cnt;
+        for (int k = k0; k < k1; k++) {
+            if (St[k] == 0) continue;
+            if (q >= i0 && q < i0 + RM_ROWS && q < fm) s_lc[q - i0] = k;
+            q++;
+        }
+        rm = min(total, fm);
+    }
+    __syncthreads();
+    if (i0 >= rm) return;
+    const int i = i0 + tid, ic = min(i, rm - 1);
+    const int mylc = s_lc[ic - i0], kbeg = s_lc[0];
+    const int *rj = Rj + s.rp;
+    const double *F = c.Farena + s.foff;
+    const long long ld = s.ld;
+    double hi = 0.0, lo = 0.0;
+    for (int kc = kbeg; kc < fn; kc += RM_XC) {
+        const int len = min(RM_XC, fn - kc);
+        __syncthreads();                                // (the previous chunk is done with)
+        for (int e = tid; e < len; e += RM_NT) s_x[e] = X[rj[kc + e]];
+        __syncthreads();
+        const double *Fp = F + ic + (long long)kc * ld;
+        for (int kk = 0; kk < len; kk++)
+            if (kc + kk >= mylc) dd_add_product(Fp[(long long)kk * ld], s_x[kk], hi, lo);
+    }
+    if (i < rm) Y[rowbase[f] + i] = hi + lo;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Z = R' Y scatters into columns that several fronts share: two kernels, no atomics.  k_rtmult_dots: every front writes the dot of
 // its column k with its rows of y into its own slot U[Rp[f] + k] (the pass-vector array of the R' solve: one writer per slot).  A
@@ -260,6 +322,13 @@ int stm_launch_rmult(const DevCtx &c, const int *flist, int nfr, int max_slab, c
     if (nfr <= 0 || max_slab <= 0) return 0;
     if (nb >= 3) hipLaunchKernelGGL(k_rmult<4>, dim3(nfr, max_slab, (nb + 3) / 4), dim3(RM_NT), 0, st, c, flist, Rj, rowbase, X, Y, B, nb);
     else hipLaunchKernelGGL(k_rmult<1>, dim3(nfr, max_slab, nb), dim3(RM_NT), 0, st, c, flist, Rj, rowbase, X, Y, B, nb);
+    return (int)hipGetLastError();
+}
+int stm_launch_rmult_dd(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *Rj, const int *rowbase, const double *X, double *Y,
+                        hipStream_t st, int nb, const RhsBatch &B)
+{
+    if (nfr <= 0 || max_slab <= 0 || nb <= 0) return 0;
+    hipLaunchKernelGGL(k_rmult_dd, dim3(nfr, max_slab, nb), dim3(RM_NT), 0, st, c, flist, Rj, rowbase, X, Y, B);
     return (int)hipGetLastError();
 }
 int stm_launch_rtmult_dots(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *rowbase, const double *Y, double *U, int absval,
