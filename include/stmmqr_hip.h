@@ -37,6 +37,8 @@ typedef long stm_long;
 #define STMMQR_ERR_DEVICE        (-5)   /* SPARSE_GPU_PROBLEM: no gfx950 device / HIP runtime error */
 #define STMMQR_ERR_RESCHEDULE    (-6)   /* stmmqr_factorize_finish: a front still had rows at the last panel the plan scheduled for it
                                            (stmmqr_plan_set_early_end); nothing is lost but this attempt -- factorize again */
+#define STMMQR_ERR_STALE         (-7)   /* stmmqr_sparseqr_refactorize: a singleton of the first values has no pivot above the tolerance
+                                           under the new ones; the object is unchanged -- make a new one */
 
 /* ================================================================================================
  * Layout-compatible mirrors of the structs that cross the seam
@@ -722,12 +724,56 @@ int stmmqr_sparseqr_solve(stmmqr_qr *qr, int system, const double *B, stm_long l
  * stmmqr_plan_solve_minnorm call: no limit on the width of a front.  Needs H. */
 int stmmqr_sparseqr_min2norm(stmmqr_qr *qr, const double *B, stm_long ldb, stm_long nrhs, double *X, stm_long ldx);
 
+/* ---- New values of the same pattern (a Newton step, a time step): stmmqr_sparseqr_refactorize ------------------------------------
+ * gives a factorized object new values.  Ax has the pattern and the storage order of the matrix the object was made from: A for
+ * stmmqr_sparseqr, the caller's A (not A') for an object from stmmqr_sparselq; a host array, or a device pointer with ax_on_device.
+ * Kept: column order and singleton set, R1's and Y's patterns, the analysis, the plan with its arenas (nothing is analysed, planned
+ * or allocated again, and also objects with keepH = 0 take new values).  Made again, so that every stmmqr_sparseqr_* call afterwards
+ * acts on the new factorization: the tolerance by the rule of the object's tol argument (tol <= -2: 20 (m + n) eps max_j |A(:,j)|_2
+ * of the NEW values, bit for bit what a new object computes; tol >= 0 stays; -2 < tol < 0 stays "none"), R1x, the Yx of
+ * stmmqr_sparseqr_y, the factors on the device, Rdead, rank, HP1inv, and of stmmqr_sparseqr_info the factorize seconds, flops,
+ * device ms and retries (the analyze seconds stay).
+ * Singletons depend on values.  The first values fixed the structure; new ones keep it valid as long as the pivot of every live
+ * singleton still exceeds the new tolerance (|a| > tol, the test of creation; dead singletons have no pivot).  That is checked on
+ * the device before anything of the old factorization is touched.  If it fails: STMMQR_ERR_STALE, the message names the first
+ * failing singleton in singleton order, its column, the value and the tolerance, and the object is unchanged -- it still answers
+ * with its earlier factorization; the caller makes a new object.  With tol = -1 the test always holds, as at creation.  Columns
+ * that were no singletons under the first values but would be under the new ones are NOT looked for: the result is a correct QR
+ * factorization all the same, only not the structure a new object would choose.
+ * STMMQR_ERR_INVALID (the message says why, the object is unchanged): null object, null Ax with a non-empty pattern, no numeric
+ * phase yet, a pattern of 2^31 or more entries (the maps below are int tables).  If the factorization itself fails after the values
+ * were accepted (device error, out of memory), the old factors are gone: the object holds no valid factorization, and qmult, solve,
+ * min2norm, solve_seminormal and stmmqr_plan_export_r through it refuse with a message that says so until a refactorization
+ * succeeds.
+ * Device work besides the factorization (stmmqr_refactor.hip): the column norms of the default tolerance (a lane per column in
+ * storage order -- the host rule's operations in the host rule's order; slow on a dense column of tens of thousands of entries,
+ * accepted for the equal bits), the split of the values into R1x and Yx, the singleton check; then ONE device-to-host copy of
+ * {norm, first stale singleton, R1x, Yx}, the only host wait before the factorization.  An object without singletons that is no LQ
+ * object factorizes straight from the caller's device pointer (a host array is uploaded once).
+ * Measured on an MI355X (tools/time_refactor.py), wall ms of the call against the analyze + factorize seconds of a new
+ * object on the same values: bcsstk14 8.5 against 3.9 + 8.9, bayer10 (1190 singleton columns) 8.0 against 8.4 + 16.2, ex18 6.1
+ * against 5.7 + 6.7, the xenon1 stand-in (no singletons) 86.9 against 270.8 + 94.0; a device pointer saves up to 0.3 ms more; the
+ * value kernels take 20 -- 40 us.
+ *   stmmqr_sparseqr_refactor_info  info[0..7] = tolerance of the last refactorization, device ms of the value kernels, device ms of
+ *                                  the factorization, wall seconds of the call, refactorizations done, stale refusals, analyses +
+ *                                  plans the object has made since its creation (stays 2), device bytes it holds beyond its plan.
+ *   stmmqr_sparseqr_refactor_maps  where the values go (no device needed; works on a symbolic-only object): counts[0..3] = entries of
+ *                                  the caller's matrix, nnz(Y), nnz(R1), n1rows; ysrc[t] = the caller's storage position of entry t
+ *                                  of Y, r1src[q] the same for R1's row form, pivsrc[k] the position of the pivot of live singleton
+ *                                  row k.  The pointers are NULL when the object has no singletons and is no LQ object (Y is then A
+ *                                  itself); without singletons an LQ object has ysrc (the transposition) and NULL for the others.
+ *                                  Any argument but qr may be NULL. */
+int stmmqr_sparseqr_refactorize(stmmqr_qr *qr, const double *Ax, int ax_on_device);
+int stmmqr_sparseqr_refactor_info(const stmmqr_qr *qr, double *info /* [8] */);
+int stmmqr_sparseqr_refactor_maps(const stmmqr_qr *qr, stm_long *counts /* [4] */, const int **ysrc, const int **r1src, const int **pivsrc);
+
 /* ---- R / H out in sparse form, LQ (STMMQR/src/qr/SparseLQ.c; prototypes SparseQR.h:282-340) ---------
  * qr_rcount / qr_rconvert / qr_trapezoidal keep the reference's names, argument lists and results (bit for bit: they move
  * data).  They read a qr_numeric on the host -- the one qr_factorize returned.  stmmqr_plan_export_r does the same for the
  * factorization a plan holds in HBM (one download): R as compressed sparse columns over the columns of the factorized matrix,
  * optionally H (one column per live reflector, unit diagonal stored, rows = the permuted row ids) and its Tau; every output
- * array is malloc'ed (stmmqr_free).  stmmqr_sparselq = SparseLQ: the QR object of A' (L = R'). */
+ * array is malloc'ed (stmmqr_free).  stmmqr_sparselq = SparseLQ: the QR object of A' (L = R'); device -2: its host half only (no
+ * device is touched; the object answers stmmqr_sparseqr_refactor_maps and the symbolic getters and never gets a numeric phase). */
 void qr_rcount(stm_qr_symbolic *QRsym, stm_qr_numeric *QRnum, stm_long n1rows, stm_long econ, stm_long n2, int getT, stm_long *Ra,
                stm_long *Rb, stm_long *H2p, stm_long *p_nh);
 void qr_rconvert(stm_qr_symbolic *QRsym, stm_qr_numeric *QRnum, stm_long n1rows, stm_long econ, stm_long n2, int getT,

@@ -24,6 +24,7 @@ class StmmqrError(RuntimeError):
 
 
 ERR_RESCHEDULE = -6                        # STMMQR_ERR_RESCHEDULE (include/stmmqr_hip.h)
+ERR_STALE = -7                             # STMMQR_ERR_STALE: SparseQR.refactorize, the singleton structure does not hold for the new values
 
 
 if not lib_path.exists():
@@ -981,6 +982,12 @@ lib.stmmqr_sparseqr_y.argtypes = [C.c_void_p, C.POINTER(c_long_p), C.POINTER(c_l
 lib.stmmqr_sparseqr_qmult.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_long, C.c_long, C.c_long, c_double_p, C.c_long]
 lib.stmmqr_sparseqr_solve.argtypes = [C.c_void_p, C.c_int, c_double_p, C.c_long, C.c_long, c_double_p, C.c_long]
 lib.stmmqr_sparseqr_min2norm.argtypes = [C.c_void_p, c_double_p, C.c_long, C.c_long, c_double_p, C.c_long]
+lib.stmmqr_sparseqr_tol.restype = C.c_double
+lib.stmmqr_sparseqr_tol.argtypes = [C.c_void_p]
+lib.stmmqr_sparseqr_refactorize.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+lib.stmmqr_sparseqr_refactor_info.argtypes = [C.c_void_p, c_double_p]
+c_int_p = C.POINTER(C.c_int)
+lib.stmmqr_sparseqr_refactor_maps.argtypes = [C.c_void_p, c_long_p, C.POINTER(c_int_p), C.POINTER(c_int_p), C.POINTER(c_int_p)]
 
 
 lib.stmmqr_sparseqr_plan.restype = C.c_void_p
@@ -1023,6 +1030,8 @@ class SparseQR:
         self._A = (np.ascontiguousarray(Ap, I64), np.ascontiguousarray(Ai, I64), np.ascontiguousarray(Ax, np.float64))
         Q = None if Quser is None else np.ascontiguousarray(Quser, I64)
         self._h = C.c_void_p()
+        self._args = dict(ordering=ordering, tol=tol, relax=relax, Quser=Quser, device=device, keep_h=keep_h)   # (refactorize(rebuild=True))
+        self._rebuilt = 0
         rp = None if relax is None else C.byref(relax)
         if symbolic_only or not keep_h:
             _check(lib.stmmqr_sparseqr_symbolic(ordering, tol, m, n, _ip(self._A[0]), _ip(self._A[1]), _dp(self._A[2]), _ip(Q), rp,
@@ -1101,9 +1110,68 @@ class SparseQR:
         self.m, self.n = int(n), int(m)
         self._A = (np.ascontiguousarray(Ap, I64), np.ascontiguousarray(Ai, I64), np.ascontiguousarray(Ax, np.float64))
         self._h = C.c_void_p()
+        self._args = dict(tol=tol, relax=relax, device=device)
+        self._rebuilt = 0
         _check(lib.stmmqr_sparselq(7, tol, m, n, _ip(self._A[0]), _ip(self._A[1]), _dp(self._A[2]), None if relax is None else C.byref(relax),
                                    device, C.byref(self._h)), "stmmqr_sparselq")
         return self
+
+    def refactorize(self, Ax=None, dev_ptr=None, rebuild=False):
+        """New values of the same pattern (stmmqr_sparseqr_refactorize): Ax, a numpy array in the storage order of the matrix the
+        object was made from (A itself also for SparseQR.lq objects), or dev_ptr, a device pointer to such values (tensor.data_ptr()).
+        Column order, singletons, analysis, plan and arenas stay; tolerance, R1, Y, factors, rank are made again.  Raises
+        StmmqrError with code ERR_STALE, the object unchanged, when a singleton of the first values has no pivot above the new
+        tolerance -- unless rebuild=True, which then makes a new native object with the same arguments from Ax and swaps it in
+        (refactor_info["rebuilt"] counts that; needs Ax: there is no host copy of device values to analyse).  Returns self."""
+        if (Ax is None) == (dev_ptr is None):
+            raise StmmqrError("refactorize: give Ax (a host array) or dev_ptr (a device pointer), one of them")
+        if dev_ptr is not None:
+            if rebuild:
+                raise StmmqrError("refactorize: rebuild=True needs host values (Ax): a device pointer leaves nothing to analyse on the host")
+            _check(lib.stmmqr_sparseqr_refactorize(self._h, C.c_void_p(int(dev_ptr)), 1), "stmmqr_sparseqr_refactorize")
+            self._A = (self._A[0], self._A[1], None)                 # (solve_seminormal needs A's values on the host)
+            return self
+        Ax = np.ascontiguousarray(Ax, np.float64)
+        if Ax.size != int(self._A[0][-1]):
+            raise StmmqrError("refactorize: Ax must hold one value per entry of the pattern")
+        rc = lib.stmmqr_sparseqr_refactorize(self._h, Ax.ctypes.data if Ax.size else None, 0)
+        if rc == ERR_STALE and rebuild:
+            a = self._args
+            if getattr(self, "_is_lq", False):
+                new = SparseQR.lq(self.n, self.m, self._A[0], self._A[1], Ax, **a)
+            else:
+                new = SparseQR(self.m, self.n, self._A[0], self._A[1], Ax, **a)
+            old, self._h, new._h = self._h, new._h, None
+            lib.stmmqr_sparseqr_free(old)
+            self._A, self._rebuilt = new._A, self._rebuilt + 1
+            return self
+        _check(rc, "stmmqr_sparseqr_refactorize")
+        self._A = (self._A[0], self._A[1], Ax.copy())
+        return self
+
+    @property
+    def refactor_info(self) -> dict:
+        """stmmqr_sparseqr_refactor_info, and "rebuilt": how often refactorize(rebuild=True) had to make a new native object"""
+        v = np.zeros(8)
+        _check(lib.stmmqr_sparseqr_refactor_info(self._h, _dp(v)), "stmmqr_sparseqr_refactor_info")
+        keys = ["tol", "ms_values", "ms_factorize", "seconds", "refactorizations", "stale", "analyses_and_plans", "device_bytes"]
+        return {**dict(zip(keys, v.tolist())), **{i: float(v[i]) for i in range(8)}, "rebuilt": self._rebuilt}
+
+    def refactor_maps(self) -> dict:
+        """stmmqr_sparseqr_refactor_maps: counts = [nz, nnz(Y), nnz(R1), n1rows] and ysrc / r1src / pivsrc (None where the native
+        pointer is NULL: no singletons and no LQ object), positions in the caller's storage order"""
+        cnt = np.zeros(4, I64)
+        y, r, p = c_int_p(), c_int_p(), c_int_p()
+        _check(lib.stmmqr_sparseqr_refactor_maps(self._h, _ip(cnt), C.byref(y), C.byref(r), C.byref(p)), "stmmqr_sparseqr_refactor_maps")
+
+        def arr(ptr, k):
+            return np.ctypeslib.as_array(ptr, shape=(max(int(k), 1),))[:int(k)].copy() if ptr else None
+        return {"counts": cnt, "ysrc": arr(y, cnt[1]), "r1src": arr(r, cnt[2]), "pivsrc": arr(p, cnt[3])}
+
+    @property
+    def tol(self) -> float:
+        """the tolerance the factorization really used (stmmqr_sparseqr_tol)"""
+        return float(lib.stmmqr_sparseqr_tol(self._h))
 
     def qmult(self, method, X):
         X = np.asfortranarray(X, dtype=np.float64)
@@ -1118,6 +1186,9 @@ class SparseQR:
         the device.  Returns (X, info), info = max over the columns of |A'r| / (|A|_F (|A|_F |x| + |b|))."""
         if getattr(self, "_is_lq", False):
             raise StmmqrError("solve_seminormal: not on the LQ object")
+        if self._A[2] is None:
+            raise StmmqrError("solve_seminormal: the object was last refactorized from a device pointer and has no host copy of A's values; "
+                              "refactorize with a host array (Ax=...) first")
         B = np.asfortranarray(B, dtype=np.float64)
         if B.ndim == 1:
             B = B.reshape(-1, 1, order="F")

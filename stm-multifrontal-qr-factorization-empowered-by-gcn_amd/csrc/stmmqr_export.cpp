@@ -20,6 +20,7 @@
 
 #include "../../include/stmmqr_hip.h"
 #include "stmmqr_internal.h"
+#include "stmmqr_sparseqr.h"
 
 namespace {
 
@@ -238,10 +239,28 @@ int stmmqr_sparselq(int ordering, double tol, stm_long m, stm_long n, const stm_
         }
         for (Long i = 0; i < m; i++) Tp[(size_t)i + 1] += Tp[(size_t)i];
         std::vector<Long> w(Tp.begin(), Tp.end() - 1);
+        // (tsrc: where in A's storage entry q of A' came from -- the object composes its value maps with it, so that
+        //  stmmqr_sparseqr_refactorize takes new values in A's own order; int tables, not built for 2^31 entries or more)
+        const bool small = nz < ((Long)1 << 31);
+        std::vector<int> tsrc(small ? (size_t)nz : 0);
         for (Long j = 0; j < n; j++)
-            for (Long p = Ap[j]; p < Ap[j + 1]; p++) { const Long q = w[(size_t)Ai[p]]++; Ti[(size_t)q] = j; Tx[(size_t)q] = Ax[p]; }
+            for (Long p = Ap[j]; p < Ap[j + 1]; p++) {
+                const Long q = w[(size_t)Ai[p]]++;
+                Ti[(size_t)q] = j; Tx[(size_t)q] = Ax[p];
+                if (small) tsrc[(size_t)q] = (int)p;
+            }
         (void)ordering;                                       // (the reference passes QR_ORDERING_DEFAULT whatever it is given, :729)
-        return stmmqr_sparseqr(7, tol, n, m, Tp.data(), Ti.data(), Tx.data(), nullptr, relax, device, out);
+        // device -2: the host half only (no device is touched, the value maps can be read); the transposed arrays end with this call,
+        // so such an object never gets a numeric phase
+        const bool host_only = device == -2;
+        int e = host_only ? stmmqr_sparseqr_symbolic(7, tol, n, m, Tp.data(), Ti.data(), Tx.data(), nullptr, relax, out)
+                          : stmmqr_sparseqr(7, tol, n, m, Tp.data(), Ti.data(), Tx.data(), nullptr, relax, device, out);
+        if (!e && host_only) { (*out)->Fp = nullptr; (*out)->Fi = nullptr; (*out)->Fx = nullptr; }
+        if (!e) {
+            e = stm_sparseqr_set_transposition(*out, small ? tsrc.data() : nullptr, nz);
+            if (e) { stmmqr_sparseqr_free(*out); *out = nullptr; }
+        }
+        return e;
     } catch (const std::bad_alloc &) {
         return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_sparselq: out of memory");
     }

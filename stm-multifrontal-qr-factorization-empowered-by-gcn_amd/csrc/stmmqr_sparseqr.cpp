@@ -26,6 +26,7 @@
 
 #include "../../include/stmmqr_hip.h"
 #include "stmmqr_internal.h"
+#include "stmmqr_sparseqr.h"
 
 bool stm_colamd_order(stm_long n_row, stm_long n_col, const stm_long *Ap, const stm_long *Ai, std::vector<stm_long> &perm);
 
@@ -82,28 +83,8 @@ void postorder_columns(Long m, Long n, const Long *Ap, const Long *Ai, std::vect
 
 }  // namespace
 
-struct stmmqr_qr {
-    Long m = 0, n = 0, n1rows = 0, n1cols = 0, rank = 0;
-    double tol = 0;
-    int ordering_used = 0;
-    std::vector<Long> Q1fill, P1inv, HP1inv, R1p, R1j;        // P1inv / HP1inv / R1*: only when n1cols > 0
-    std::vector<double> R1x;
-    std::vector<Long> Yp, Yi;                                 // the matrix handed to the numeric phase when singletons exist
-    std::vector<double> Yx;
-    stmmqr_analysis *sym = nullptr;
-    stmmqr_plan *plan = nullptr;
-    stmmqr_stats stats = {};
-    int keep_h = 1;                                           // stmmqr_sparseqr_set_keep_h: 0 = R only (no Q-apply)
-    std::vector<char> Rdead;                                  // of the multifrontal part (n - n1cols)
-    double ana_seconds = 0, fac_seconds = 0, sym_info[8] = {};
-    const Long *Fp = nullptr, *Fi = nullptr;                  // what the numeric phase factorizes (A or Y)
-    const double *Fx = nullptr;
-    ~stmmqr_qr()
-    {
-        if (plan) stmmqr_plan_destroy(plan);
-        if (sym) stmmqr_analysis_free(sym);
-    }
-};
+// a refactorization failed after it had given the old factors up (stmmqr_sparseqr_refactorize)
+#define NO_FACTORIZATION "the object holds no valid factorization (a refactorization failed): refactorize again"
 
 extern "C" {
 
@@ -143,6 +124,11 @@ static int sparseqr_impl(int ordering, double tol, Long m, Long n, const Long *A
     const bool fill_reducing = (ordering == COLAMD);
     std::unique_ptr<stmmqr_qr> QR(new stmmqr_qr());
     QR->m = m; QR->n = n;
+    // what a refactorization needs of the call: the tolerance rule, the column pointers (column norms of new values), and whether
+    // the maps of the split below fit their int tables
+    QR->tol_arg = tol; QR->nz = Ap[n];
+    QR->maps_too_large = Ap[n] >= ((Long)1 << 31);
+    if (numeric >= 0) QR->Ap0.assign(Ap, Ap + n + 1);
     if (tol <= -2) tol = stm_qr_default_tol(m, n, Ap, Ax);
     if (tol < 0) tol = -1;                                                                        // QR_NO_TOL (SparseQR.c:131-135)
     QR->tol = tol;
@@ -266,6 +252,9 @@ static int sparseqr_impl(int ordering, double tol, Long m, Long n, const Long *A
             QR->R1x.assign((size_t)std::max<Long>(tot, 1), 0.0);
         }
         std::vector<Long> fill(R1p.begin(), R1p.end());
+        // (the storage position of every entry goes where its value goes: ysrc / r1src, stmmqr_sparseqr_refactorize)
+        const bool maps = !QR->maps_too_large;
+        if (maps) QR->r1src.assign(QR->R1x.size(), 0);
         QR->Yp.assign((size_t)n2 + 1, 0);
         for (Long k = 0; k < n1cols; k++) {
             const Long j = Q1[(size_t)k];
@@ -274,6 +263,7 @@ static int sparseqr_impl(int ordering, double tol, Long m, Long n, const Long *A
                 if (inew >= n1rows) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr: internal (singleton column reaches a live row)");
                 const Long q = fill[(size_t)inew]++;
                 QR->R1j[(size_t)q] = k; QR->R1x[(size_t)q] = Ax[p];
+                if (maps) QR->r1src[(size_t)q] = (int)p;
             }
         }
         for (Long k = n1cols; k < n; k++) {
@@ -281,12 +271,25 @@ static int sparseqr_impl(int ordering, double tol, Long m, Long n, const Long *A
             QR->Yp[(size_t)(k - n1cols)] = (Long)QR->Yi.size();
             for (Long p = Ap[j]; p < Ap[j + 1]; p++) {
                 const Long inew = QR->P1inv[(size_t)Ai[p]];
-                if (inew < n1rows) { const Long q = fill[(size_t)inew]++; QR->R1j[(size_t)q] = k; QR->R1x[(size_t)q] = Ax[p]; }
-                else { QR->Yi.push_back(inew - n1rows); QR->Yx.push_back(Ax[p]); }
+                if (inew < n1rows) {
+                    const Long q = fill[(size_t)inew]++;
+                    QR->R1j[(size_t)q] = k; QR->R1x[(size_t)q] = Ax[p];
+                    if (maps) QR->r1src[(size_t)q] = (int)p;
+                } else {
+                    QR->Yi.push_back(inew - n1rows); QR->Yx.push_back(Ax[p]);
+                    if (maps) QR->ysrc.push_back((int)p);
+                }
             }
         }
         QR->Yp[(size_t)n2] = (Long)QR->Yi.size();
+        if (maps) {
+            // a live singleton's pivot is the first entry of its row of R1: its column was the first to reach that row
+            QR->pivsrc.assign((size_t)std::max<Long>(n1rows, 1), 0);
+            for (Long i = 0; i < n1rows; i++) QR->pivsrc[(size_t)i] = QR->r1src[(size_t)R1p[(size_t)i]];
+            QR->have_maps = true;
+        }
         if (QR->Yi.empty()) { QR->Yi.push_back(0); QR->Yx.push_back(0.0); }
+        if (maps && QR->ysrc.empty()) QR->ysrc.push_back(0);
         Fp = QR->Yp.data(); Fi = QR->Yi.data(); Fx = QR->Yx.data(); Fq = nullptr;          // analysis of Y: ordering FIXED (:360)
     }
 
@@ -306,10 +309,34 @@ static int sparseqr_impl(int ordering, double tol, Long m, Long n, const Long *A
     return 0;
 }
 
+// after a factorization by the plan (the first one here, later ones in stmmqr_sparseqr_refactorize): Rdead, HPinv and the scalars
+// come back, rank and HP1inv follow
+int stm_sparseqr_after_factorization(stmmqr_qr *QR)
+{
+    const Long m = QR->m, n1cols = QR->n1cols, n1rows = QR->n1rows;
+    const stm_qr_symbolic *S = stmmqr_analysis_symbolic(QR->sym);
+    Long scal[4] = {0, 0, 0, 0};
+    QR->Rdead.assign((size_t)std::max<Long>(S->n, 1), 0);
+    std::vector<Long> HPinv((size_t)std::max<Long>(S->m, 1));
+    const int e = stmmqr_plan_download(QR->plan, nullptr, nullptr, QR->Rdead.data(), nullptr, nullptr, nullptr, HPinv.data(), nullptr, nullptr, scal, nullptr);
+    if (e) return e;
+    QR->rank = n1rows + scal[1];                                                            // n1rows + rank1 (SparseQR.c:393)
+    if (n1cols > 0 && QR->keep_h) {                                                         // (R only: no HPinv, no Q-apply)
+        QR->HP1inv.assign((size_t)std::max<Long>(m, 1), 0);
+        for (Long i = 0; i < m; i++) {
+            const Long k = QR->P1inv[(size_t)i];
+            QR->HP1inv[(size_t)i] = (k < n1rows) ? k : HPinv[(size_t)(k - n1rows)] + n1rows;
+        }
+    }
+    return 0;
+}
+
 static int numeric_impl(stmmqr_qr *QR, int device)
 {
     if (QR->plan) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_numeric: already factorized");
-    const Long m = QR->m, n = QR->n, n1cols = QR->n1cols, n1rows = QR->n1rows, n2 = n - n1cols;
+    if (!QR->Fp) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_numeric: the object was made as the host half of stmmqr_sparselq (device -2)");
+    const Long n = QR->n, n1cols = QR->n1cols, n2 = n - n1cols;
+    QR->device = device;
     const Long *Fp = QR->Fp, *Fi = QR->Fi;
     const double *Fx = QR->Fx;
     const double tol = QR->tol;
@@ -330,20 +357,9 @@ static int numeric_impl(stmmqr_qr *QR, int device)
     const Long ntol = (n1cols > 0) ? n2 : n;                                              // (SparseQR.c:349 / :371)
     e = stmmqr_factorize_device(QR->plan, Fp, Fi, Fx, 0, tol, ntol, &QR->stats);
     if (e) return e;
-    Long scal[4] = {0, 0, 0, 0};
-    QR->Rdead.assign((size_t)std::max<Long>(S->n, 1), 0);
-    std::vector<Long> HPinv((size_t)std::max<Long>(S->m, 1));
-    e = stmmqr_plan_download(QR->plan, nullptr, nullptr, QR->Rdead.data(), nullptr, nullptr, nullptr, HPinv.data(), nullptr, nullptr, scal, nullptr);
+    e = stm_sparseqr_after_factorization(QR);
     if (e) return e;
     QR->fac_seconds = wall() - t_fac;
-    QR->rank = n1rows + scal[1];                                                            // n1rows + rank1 (SparseQR.c:393)
-    if (n1cols > 0 && QR->keep_h) {                                                         // (R only: no HPinv, no Q-apply)
-        QR->HP1inv.assign((size_t)std::max<Long>(m, 1), 0);
-        for (Long i = 0; i < m; i++) {
-            const Long k = QR->P1inv[(size_t)i];
-            QR->HP1inv[(size_t)i] = (k < n1rows) ? k : HPinv[(size_t)(k - n1rows)] + n1rows;
-        }
-    }
     return 0;
 }
 
@@ -446,11 +462,60 @@ int stmmqr_sparseqr_y(const stmmqr_qr *qr, const stm_long **Yp, const stm_long *
     return 0;
 }
 
+// ---- new values of the same pattern: the host-side getters (the call itself is stmmqr_refactor.hip) ----
+int stmmqr_sparseqr_refactor_info(const stmmqr_qr *qr, double *info)
+{
+    if (!qr || !info) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_refactor_info: null argument");
+    for (int k = 0; k < 8; k++) info[k] = qr->rf_info[k];
+    info[6] = (qr->sym ? 1.0 : 0.0) + (qr->plan ? 1.0 : 0.0);                      // (made once each, never again)
+    return 0;
+}
+
+int stmmqr_sparseqr_refactor_maps(const stmmqr_qr *qr, stm_long *counts, const int **ysrc, const int **r1src, const int **pivsrc)
+{
+    if (!qr) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_refactor_maps: null object");
+    if (qr->Ap0.empty()) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_refactor_maps: the object holds a column order only");
+    const bool sing = qr->n1cols > 0;
+    if (counts) {
+        counts[0] = qr->nz; counts[1] = sing ? qr->Yp[(size_t)(qr->n - qr->n1cols)] : qr->nz;
+        counts[2] = sing ? qr->R1p[(size_t)qr->n1rows] : 0; counts[3] = qr->n1rows;
+    }
+    if (ysrc) *ysrc = qr->have_maps ? qr->ysrc.data() : nullptr;
+    if (r1src) *r1src = qr->have_maps && sing ? qr->r1src.data() : nullptr;
+    if (pivsrc) *pivsrc = qr->have_maps && sing ? qr->pivsrc.data() : nullptr;
+    return 0;
+}
+
+// the transposition of stmmqr_sparselq (tsrc[q]: position in A of entry q of A'): from here on the maps speak of A's storage
+int stm_sparseqr_set_transposition(stmmqr_qr *qr, const int *tsrc, stm_long nz)
+{
+    if (!qr || nz != qr->nz || qr->is_lq) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparselq: internal (transposition)");
+    qr->is_lq = true;
+    if ((!tsrc && nz > 0) || qr->maps_too_large) return 0;
+    try {
+        qr->tsrc.assign(tsrc, tsrc + nz);
+        if (qr->have_maps) {
+            const stm_long ny = qr->Yp[(size_t)(qr->n - qr->n1cols)], nr1 = qr->R1p[(size_t)qr->n1rows];   // (placeholders beyond)
+            for (stm_long t = 0; t < ny; t++) qr->ysrc[(size_t)t] = tsrc[qr->ysrc[(size_t)t]];
+            for (stm_long q = 0; q < nr1; q++) qr->r1src[(size_t)q] = tsrc[qr->r1src[(size_t)q]];
+            for (stm_long k = 0; k < qr->n1rows; k++) qr->pivsrc[(size_t)k] = tsrc[qr->pivsrc[(size_t)k]];
+        } else {
+            qr->ysrc = qr->tsrc;                                                   // (no singletons: Y is A')
+            if (qr->ysrc.empty()) qr->ysrc.push_back(0);
+            qr->have_maps = true;
+        }
+    } catch (const std::bad_alloc &) {
+        return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_sparselq: out of memory");
+    }
+    return 0;
+}
+
 // ---- QR_qmult (SparseQR.c:1838-2020): X is nrow x ncol (ldx), Y gets the same shape (ldy) ----
 int stmmqr_sparseqr_qmult(stmmqr_qr *qr, int method, const double *X, stm_long ldx, stm_long nrow, stm_long ncol, double *Y, stm_long ldy)
 {
     if (!qr || !X || !Y || method < 0 || method > 3) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_qmult: bad arguments");
     if (!qr->keep_h) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_qmult: the factorization keeps no Householder vectors (keepH = 0)");
+    if (!qr->valid) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_qmult: " NO_FACTORIZATION);
     const Long m = qr->m, n1 = qr->n1rows;
     const bool left = method <= 1;
     if ((left ? nrow : ncol) != m) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_qmult: X does not match the rows of A");
@@ -515,6 +580,7 @@ int stmmqr_sparseqr_qmult(stmmqr_qr *qr, int method, const double *X, stm_long l
 int stmmqr_sparseqr_solve(stmmqr_qr *qr, int system, const double *B, stm_long ldb, stm_long nrhs, double *X, stm_long ldx)
 {
     if (!qr || !B || !X || system < 0 || system > 3 || nrhs < 0) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_solve: bad arguments");
+    if (!qr->valid) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_solve: " NO_FACTORIZATION);
     const Long m = qr->m, n = qr->n, n1r = qr->n1rows, n1c = qr->n1cols, n2 = n - n1c, m2 = m - n1r;
     const Long brows = system <= 1 ? m : n, xrows = system <= 1 ? n : m;
     if (ldb < brows || ldx < xrows) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_solve: bad leading dimension");
@@ -578,6 +644,7 @@ int stm_sparseqr_min2norm(stmmqr_qr *qr, const double *B, stm_long ldb, stm_long
 {
     if (!qr || !B || !X || nrhs < 0) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_min2norm: bad arguments");
     if (!qr->keep_h) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_min2norm: the factorization keeps no Householder vectors (keepH = 0)");
+    if (!qr->valid) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_min2norm: " NO_FACTORIZATION);
     const Long m = qr->m, n = qr->n, n1r = qr->n1rows, n1c = qr->n1cols, n2 = n - n1c, m2 = m - n1r;
     if (ldb < n || ldx < m) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_sparseqr_min2norm: bad leading dimension");
     if (nrhs == 0) return 0;
