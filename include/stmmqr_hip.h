@@ -784,6 +784,34 @@ stm_long qr_trapezoidal(stm_long n, stm_long *Rp, stm_long *Ri, double *Rx, stm_
                         stm_sparse_common *cc);
 int stmmqr_plan_export_r(stmmqr_plan *plan, const stm_qr_symbolic *sym, stm_long econ, stm_long **Rp, stm_long **Ri, double **Rx,
                          stm_long *nh, stm_long **Hp, stm_long **Hi, double **Hx, double **HTau);
+
+/* R of the held factorization as a sparse matrix, made ON THE DEVICE from the resident factors: nothing is downloaded but the entries
+ * kept, and with on_device nothing at all.  The matrix is the m x ncol one stmmqr_plan_export_r defines: rows numbered front by front
+ * over the live pivots, columns those of the factorized matrix in its own order (the caller applies Qfill); an entry is kept if
+ * row < econ, column < ncol and value != 0.0 (exact zeros are dropped, -0.0 included); dead pivot columns keep the rows above them.
+ * ncol = n: all of R; ncol < n: its leading columns -- R of A for the plan of [A B] of the least-squares object (it only filters: no
+ * carried-view condition).  Both forms describe the same matrix; in compressed rows, rows >= min(econ, rows of R) are empty.
+ * Two calls: idx == NULL and val == NULL counts -- ptr and info are written; with both and cap >= nnz it fills.  cap < nnz:
+ * STMMQR_ERR_INVALID naming nnz and cap, ptr and info written, idx / val untouched, the plan stays usable.  A fill call does not
+ * depend on an earlier count call (it counts again).  on_device: ptr, idx and val are device pointers; else host arrays, and nnz
+ * entries cross the bus.  info is always a host array: info[0] = nnz, info[1] = the stored entries visited before the zero test (rows
+ * < econ, columns < ncol), info[2] = the rows of R, info[3] = 0.  Complete on return (the plan's stream is synchronised).
+ * Deterministic: positions come from scans and from ranks within a wave's ballot, no atomics -- the same bits run after run, and the
+ * bits of stmmqr_plan_export_r.  ptr and every offset are 64-bit.
+ * Reads R only: plans with and without H.  H itself is not exported here -- that stays with stmmqr_plan_export_r's host path.
+ * Memory, made at the first call of a form and kept with the plan (a plan that never calls this allocates nothing for it): compressed
+ * columns 16 bytes per entry of Rj (two int counts and a 64-bit offset per slot) and the transpose of Rj (4 bytes per entry + 4 per
+ * column, shared with stmmqr_plan_rmult's trans = 1); compressed rows 8 bytes per row of the matrix.  With host arrays the device
+ * images of ptr, idx and val (16 bytes per entry kept) live for the length of the call.  With the level-wise scratch
+ * (STMMQR_RESIDENT_CACHE=0) the count walk and the fill walk each put the levels back into front form.
+ * Refusals (STMMQR_ERR_INVALID, the message says why, the plan stays usable): null plan or nothing factorized, form not 0 or 1, ncol
+ * outside [0, n], econ < 0, cap < 0, ptr or info NULL, exactly one of idx / val NULL, a plan that does not hold the whole tree. */
+#define STMMQR_RSPARSE_CSC 0   /* ptr[ncol + 1], idx = row of R,    rows ascending within a column            */
+#define STMMQR_RSPARSE_CSR 1   /* ptr[m + 1],    idx = column of R, front order (k = 0 .. fn-1) within a row */
+int stmmqr_plan_r_sparse(stmmqr_plan *plan, int form, stm_long ncol, stm_long econ, stm_long *ptr, stm_long *idx, double *val, stm_long cap,
+                         stm_long *info /* [4], always a host array */, int on_device);
+/* the HIP device the plan lives on -- where a caller allocates what it hands over with on_device; -1 for a null plan */
+int stmmqr_plan_device_index(const stmmqr_plan *plan);
 int stmmqr_sparselq(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
                     const stmmqr_relax *relax, int device, stmmqr_qr **out);
 

@@ -644,6 +644,15 @@ class HipQR:
                                      int(bool(permuted)), 0), "stmmqr_plan_rmult")
         return Y[:, 0] if np.ndim(X) == 1 else Y
 
+    def r_sparse(self, form: str = "csc", ncol=None, econ=None, device: bool = False):
+        """R of the held factorization as a sparse matrix made on the device (stmmqr_plan_r_sparse): form "csc" (rows ascending within
+        a column: the arrays of export_r, bit for bit) or "csr"; the leading ncol columns (default all) and the rows below econ
+        (default all); exact zeros dropped.  Rows are numbered front by front over the live pivots, columns are those of the
+        factorized matrix (apply Qfill).  device=False: {"ptr", "idx", "val", "shape", "info"} as numpy arrays, info = (nnz, stored
+        entries visited, rows of R, 0); device=True: a torch.sparse_csc_tensor / sparse_csr_tensor (m, ncol) written on the plan's
+        device -- nothing crosses the bus.  Reads R only."""
+        return _r_sparse(self._h, self.sym["m"], self.sym["n"], form, ncol, econ, device)
+
     def condest(self, kind: int = 1, iters: int = 0, ncol=None, with_vector: bool = False) -> dict:
         """The condition of R over its live pivot columns -- of A(:, live) -- estimated on the device (stmmqr_plan_condest).  kind 1:
         the one-norm, exact |R_live|_1 times Hager / Higham's estimate of |R_live^-1|_1 (LAPACK's dtrcon convention); kind 2: the
@@ -995,6 +1004,8 @@ lib.stmmqr_sparseqr_plan.argtypes = [C.c_void_p]
 lib.stmmqr_plan_export_r.argtypes = [C.c_void_p, C.POINTER(QrSymbolicC), C.c_long, C.POINTER(c_long_p), C.POINTER(c_long_p),
                                      C.POINTER(c_double_p), c_long_p, C.POINTER(c_long_p), C.POINTER(c_long_p), C.POINTER(c_double_p),
                                      C.POINTER(c_double_p)]
+lib.stmmqr_plan_r_sparse.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, c_long_p, C.c_int]
+lib.stmmqr_plan_device_index.argtypes = [C.c_void_p]
 lib.stmmqr_sparselq.argtypes = [C.c_int, C.c_double, C.c_long, C.c_long, c_long_p, c_long_p, c_double_p, C.POINTER(Relax), C.c_int,
                                 C.POINTER(C.c_void_p)]
 lib.stmmqr_free.restype = None
@@ -1005,6 +1016,40 @@ def _take(ptr, count, dtype):
     out = np.ctypeslib.as_array(ptr, shape=(max(count, 1),))[:count].astype(dtype, copy=True)
     lib.stmmqr_free(C.cast(ptr, C.c_void_p))
     return out
+
+
+R_SPARSE_FORMS = {"csc": 0, "csr": 1}
+
+
+def _r_sparse(plan, m, n, form, ncol, econ, device):
+    """stmmqr_plan_r_sparse on a plan handle of an m x n factorization: the count call, the arrays, the fill call.  device=False:
+    {"ptr", "idx", "val", "shape", "info"} as numpy arrays; device=True: a torch.sparse_csc_tensor / sparse_csr_tensor of shape
+    (m, ncol) whose int64 / float64 tensors live on the plan's device and were written there."""
+    if form not in R_SPARSE_FORMS:
+        raise StmmqrError(f"r_sparse: form {form!r} is neither 'csc' nor 'csr'")
+    code = R_SPARSE_FORMS[form]
+    ncol = n if ncol is None else int(ncol)
+    econ = m if econ is None else int(econ)
+    nptr = max((ncol if code == 0 else m) + 1, 1)
+    info = np.zeros(4, I64)
+    ptr = np.zeros(nptr, I64)
+    _check(lib.stmmqr_plan_r_sparse(plan, code, ncol, econ, ptr.ctypes.data, None, None, 0, _ip(info), 0), "stmmqr_plan_r_sparse")
+    nnz = int(info[0])
+    if not device:
+        idx, val = np.zeros(max(nnz, 1), I64), np.zeros(max(nnz, 1))
+        _check(lib.stmmqr_plan_r_sparse(plan, code, ncol, econ, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, nnz, _ip(info), 0),
+               "stmmqr_plan_r_sparse")
+        return {"ptr": ptr, "idx": idx[:nnz], "val": val[:nnz], "shape": (m, ncol), "info": info}
+    import torch
+    dev = torch.device("cuda", int(lib.stmmqr_plan_device_index(plan)))
+    tptr = torch.empty(nptr, dtype=torch.int64, device=dev)
+    tidx = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
+    tval = torch.empty(max(nnz, 1), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)
+    _check(lib.stmmqr_plan_r_sparse(plan, code, ncol, econ, tptr.data_ptr(), tidx.data_ptr(), tval.data_ptr(), nnz, _ip(info), 1),
+           "stmmqr_plan_r_sparse")
+    make = torch.sparse_csc_tensor if code == 0 else torch.sparse_csr_tensor
+    return make(tptr, tidx[:nnz], tval[:nnz], size=(m, ncol))
 
 
 def _symbolic_dict(S, m, n) -> dict:
@@ -1101,6 +1146,12 @@ class SparseQR:
             hnz = int(out["Hp"][-1])
             out["Hi"], out["Hx"], out["HTau"] = _take(Hi, hnz, I64), _take(Hx, hnz, np.float64), _take(Ht, nh.value, np.float64)
         return out
+
+    def r_sparse(self, form: str = "csc", ncol=None, econ=None, device: bool = False):
+        """HipQR.r_sparse on the object's plan: R of the multifrontal part, as export_r gives it (R1 of the singletons is not part of
+        it), without the download -- and with device=True as a torch sparse tensor that never left the device."""
+        S = lib.stmmqr_sparseqr_symbolic_view(self._h).contents
+        return _r_sparse(lib.stmmqr_sparseqr_plan(self._h), int(S.m), int(S.n), form, ncol, econ, device)
 
     @classmethod
     def lq(cls, m, n, Ap, Ai, Ax, tol=-2.0, relax: Relax | None = None, device=-1):
@@ -1331,6 +1382,12 @@ class LeastSquares:
         """after solve(): the condition of A(:, live) from the R the object holds (stmmqr_ls_condest; HipQR.condest with ncol = n)"""
         return _condest_dict(lambda out, v: lib.stmmqr_ls_condest(self._h, int(kind), int(iters), out, v, 0), "stmmqr_ls_condest", self.n,
                              with_vector)
+
+    def r_sparse(self, form: str = "csc", ncol=None, econ=None, device: bool = False):
+        """after solve(): R of A -- the leading n columns of the R of [A B] the object holds (HipQR.r_sparse, ncol = n by default) -- in
+        the column order of the factorization"""
+        S = lib.stmmqr_ls_symbolic_view(self._h).contents
+        return _r_sparse(lib.stmmqr_ls_plan(self._h), int(S.m), int(S.n), form, self.n if ncol is None else ncol, econ, device)
 
     def nullspace(self) -> np.ndarray:
         """after solve(): the null vectors of A as the rank test saw it, n x d in A's column order (stmmqr_ls_nullspace; HipQR.nullspace

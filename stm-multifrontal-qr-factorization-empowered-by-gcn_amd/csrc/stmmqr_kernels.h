@@ -181,6 +181,21 @@ int stm_launch_rtmult_gather(const int *cp, const int *slot, const double *U, do
 int stm_launch_ce_reduce(int what, const double *a, const int *idx, const double *b, int r, double *out, hipStream_t st);
 int stm_launch_ce_map(int what, double *a, const int *idx, double *dst, int r, double d, hipStream_t st);
 int stm_launch_ce_vector(const double *x, const int *qfill, double *out, int ncol, double d, hipStream_t st);
+// R as a sparse matrix in device memory (stmmqr_rsparse.hip), a tree level per launch of the walks.  Columns: count_cols writes every
+// slot's kept / visited entries (rows < econ <= m, columns < ncol; max_slab = most column slabs of STM_RM_COLS), item_sums + scan turn
+// them into ptr (nitems + 1) and info (4), slot_offsets into every slot's start, fill_cols writes idx / val.  Rows: rows(fill = 0)
+// counts per row of R (cnt / vis: m ints each, zeroed by the caller; max_slab = most row slabs of STM_RM_ROWS), item_sums (cp nullptr)
+// + scan, rows(fill = 1).  part: one entry per 256 items.  Every offset is 64-bit.
+int stm_launch_rs_count_cols(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *Rj, const int *rowbase, int ncol, int econ,
+                             int *cnt, int *vis, hipStream_t st);
+int stm_launch_rs_fill_cols(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *Rj, const int *rowbase, int ncol, int econ,
+                            const long long *off, long long *idx, double *val, hipStream_t st);
+int stm_launch_rs_rows(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *Rj, const int *rowbase, int ncol, int econ,
+                       int *cnt, int *vis, const long long *ptr, long long *idx, double *val, int fill, hipStream_t st);
+int stm_launch_rs_item_sums(const int *cp, const int *slot, const int *cnt, const int *vis, int nitems, long long *ptr, long long *part,
+                            hipStream_t st);
+int stm_launch_rs_scan(long long *ptr, long long nitems, const long long *part, int nparts, long long rtot, long long *info, hipStream_t st);
+int stm_launch_rs_slot_offsets(const int *cp, const int *slot, const int *cnt, const long long *ptr, long long *off, int ncol, hipStream_t st);
 // null-space basis of R and the minimum-norm projector (stmmqr_nullspace.hip).  N is ncol x d (ld = ncol, R's column order), G = N'N
 // and its Cholesky factor L are d x d (ld = d): the blocks below the diagonal in place, the 32 x 32 diagonal blocks of L in Ld (1024
 // doubles each, the identity beyond d).  Every offset into N, G and the partial sums is 64-bit.

@@ -1,7 +1,8 @@
 // stmmqr_resident.h -- the state of the operations on the resident factors (stmmqr_plan::res), sorted by how long it lives, and what
-// their five host units share (included by stmmqr_plan.h, after DevBuf):
+// their six host units share (included by stmmqr_plan.h, after DevBuf):
 //   stmmqr_rfactor.cpp     the front form, the row map, the passes over the tree; qmult, rsolve, solve, solve_minnorm, solve_carried
 //   stmmqr_rcond.cpp       products with R and R', the condition estimate
+//   stmmqr_rsparse.cpp     R out as compressed columns / rows in device memory
 //   stmmqr_rnull.cpp       the null-space basis of R, its Gram matrix and Cholesky factor, the minimum-norm projector
 //   stmmqr_rcov.cpp        the selected inverse: variances, leverages, covariance entries
 //   stmmqr_seminormal.cpp  products with A, the seminormal solves, the minimum-norm forwarder of the SparseQR object
@@ -15,7 +16,7 @@ struct ResidentState {
     // static maps were built from (ensure_rowmap rebuilds them when the plan's has moved on); rm_gen / rmt_gen the same for the
     // parts that the first product with R / with R' adds.  The planner itself writes the scratch layout (stmmqr_schedule.cpp).
     struct Schedule {
-        long gen = -1, rm_gen = -1, rmt_gen = -1;
+        long gen = -1, rm_gen = -1, rmt_gen = -1, rjt_gen = -1;   // (rjt_gen: the transpose of Rj alone, ensure_rj_transpose)
         restab::LevelTables T;                          // dynamic LDS per level, split fronts, T4 bookkeeping, buffer sizes
         std::vector<int> rm_rslab, rm_cslab;            // per level the most row slabs (R x) / column slabs (R' y) of a front
         DevBuf<int> d_Rj, d_PLinv, d_Qfill;             // the static integer maps
@@ -24,6 +25,10 @@ struct ResidentState {
         DevBuf<RtDesc> d_rtb;                           // T.rtb
         DevBuf<int> d_Dq, d_Rm;                         // reflector numbering of a level's split fronts / their rows of R (k_rbig_*)
         DevBuf<int> d_rtLc, d_rtRm;                     // live pivot columns of a level's rtbig fronts (T.rtlc_ints) / their counts
+        // R as a sparse matrix (stmmqr_rsparse.cpp), made by the first call of a form and kept: per slot of Rj its kept and visited
+        // entries (two ints) and its start (64-bit); per row of R the same two counts; a partial sum per 256 items, the four of info
+        DevBuf<int> d_rsSlot, d_rsRow;
+        DevBuf<long long> d_rsOff, d_rsPart, d_rsInfo;
         // grouped split Q-apply (k_qbig_step4): allocated at the first Q-apply that wants it (t4_tried); t4_ok: there was room
         bool t4_ok = false, t4_tried = false;
         DevBuf<Qt4ItemHost> d_t4items;
@@ -113,5 +118,6 @@ int r_vectors(stmmqr_plan &P, const double *Y, double *X, int nb, bool through_q
 int rt_vectors(stmmqr_plan &P, const double *Z, double *Y, int nb, bool through_qfill);
 int ensure_rmult(stmmqr_plan &P);
 int ensure_rtmult(stmmqr_plan &P);
+int ensure_rj_transpose(stmmqr_plan &P);                        // d_rmcp / d_rmslot alone (what ensure_rtmult makes besides its vectors)
 int rmult_pass(stmmqr_plan &P, const double *X, double *Y, int nb, int twofold = 0);    // twofold: row sums carried in two doubles
 int rtmult_pass(stmmqr_plan &P, const double *Y, double *Z, int nb, int absval = 0);

@@ -474,12 +474,21 @@ int ensure_rtmult(stmmqr_plan &P)
     PASS(ensure_rmult(P));
     LCHK(ensure_rt_buffers(P));
     if (S.rmt_gen == P.sched_gen) return 0;
+    PASS(ensure_rj_transpose(P));
+    S.rmt_gen = P.sched_gen;
+    return 0;
+}
+// the transpose of Rj on the device, for whoever walks a column of R through its fronts (R' y, the sparse R)
+int ensure_rj_transpose(stmmqr_plan &P)
+{
+    auto &S = P.res.sched;
+    if (S.rjt_gen == P.sched_gen) return 0;
     std::vector<int> cp, slot;
     restab::rj_transpose(P.Rj, P.n, cp, slot);
     LCHK(S.d_rmslot.upload(slot, P.stream));
     LCHK(S.d_rmcp.upload(cp, P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));                    // (cp / slot are local)
-    S.rmt_gen = P.sched_gen;
+    S.rjt_gen = P.sched_gen;
     return 0;
 }
 // nb vectors X (device, R's column order, stride n) -> Y (device, R's row order, stride m) = R X; rows beyond the rank are zero
