@@ -583,6 +583,7 @@ int stm_launch_panel_ca_pc(const DevCtx &c, const int *flist, const int *plist, 
     const int uy = (umaxsl + rspw - 1) / rspw;
     const long total = (long)n0 * nw + (long)uncb * uy * unfr;
     if (total > 0x7fffffffL) return -1;
+    stm_report_rider_launch(c, "k_panel_ca_pc", unfr, uncb, umaxsl, rspw, uy);
     hipLaunchKernelGGL(k_panel_ca_pc, dim3((unsigned)total), dim3(CA_NT), ca_pc_lds_bytes(), st, c, flist, plist, n0, nw, defer_ok, uflist, uplist,
                        ucb0, uncb, uy, Wp, uwpoff, rspw);
     for (int i = n0; i < nfr; i += K)

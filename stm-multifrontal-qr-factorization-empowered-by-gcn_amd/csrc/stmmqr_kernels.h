@@ -1,6 +1,7 @@
 // stmmqr_kernels.h -- kernel argument block and launcher prototypes (host <-> the kernel translation units: stmmqr_kdev.h lists them)
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <stdio.h>
 #include "stmmqr_device.h"
 
 // Everything a kernel needs, passed by value.  Pointers are device pointers.
@@ -59,7 +60,17 @@ struct DevCtx {
                                //  16384 no wave-pipelined panels (short panels through the multi-workgroup pipeline too)
                                //  32768 timeline of the block-0 role (tests: how many workgroup sets ran it)
                                //  65536 host only: one stderr line per front of every pair / quad sweep launch (tests)
+                               //  131072 host only: one stderr line per launch that carries riders (stm_report_rider_launch; tests)
 };
+
+// STMMQR_DBG bit 131072: what a launcher of riders decided -- the kernel that hosts them, the riders' fronts, column blocks and
+// slabs of the launch, the slabs per rider workgroup and the slab groups.  Host code; no kernel reads the bit.
+#define STM_DBG_RIDER_LAUNCH 131072
+static inline void stm_report_rider_launch(const DevCtx &c, const char *host, int unfr, int uncb, int umaxsl, int rspw, int uy)
+{
+    if (c.dbg & STM_DBG_RIDER_LAUNCH)
+        fprintf(stderr, "[rider launch] host %s unfr %d uncb %d umaxsl %d rspw %d uy %d\n", host, unfr, uncb, umaxsl, rspw, uy);
+}
 
 int stm_configure_kernels(void);       // (stmmqr_panel.hip; calls the other translation units' stm_configure_*)
 int stm_update_lds_bytes(void);

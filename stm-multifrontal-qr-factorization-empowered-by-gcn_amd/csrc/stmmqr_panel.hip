@@ -1556,6 +1556,7 @@ int stm_launch_panel_pc(const DevCtx &c, const int *flist, const int *plist, int
         if (force > 0) rspw = force;
     }
     const int uy = (umaxsl + rspw - 1) / rspw;
+    stm_report_rider_launch(c, "k_panel_pc", unfr, uncb, umaxsl, rspw, uy);
     hipLaunchKernelGGL(k_panel_pc, dim3(nfr > uncb ? nfr : uncb, nsub > uy ? nsub : uy, 1 + unfr), dim3(NTP), bytes, st, c, flist,
                        plist, nfr, nsub, defer_ok, lds_arg, uflist, uplist, ucb0, Wp, uwpoff, rspw);
     return (int)hipGetLastError();

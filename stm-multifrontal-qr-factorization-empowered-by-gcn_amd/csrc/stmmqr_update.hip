@@ -968,11 +968,13 @@ int stm_launch_update_fw(const DevCtx &c, const int *flist, const int *plist, in
         // share their CU with a second workgroup, so less of a descriptor chain is exposed than in the panel launch)
         const int rspw = (int)knobs::once<knobs::K_RSPW_W>();
         const int uy = (maxsl + rspw - 1) / rspw;
+        stm_report_rider_launch(c, "k_upd_b0w", nfr, rest > 0 ? rest : 0, maxsl, rspw, rest > 0 ? uy : 0);
         hipLaunchKernelGGL(k_upd_b0w, dim3(maxsl > rest ? maxsl : rest, rest > 0 ? uy : 1, rest > 0 ? 2 * nfr : nfr), dim3(NT),
                            stm_update_b0_lds_bytes(), st, c, flist, plist, nfr, maxsl, rest > 0 ? rest : 0, Wp, wpoff, wcnt, wflag, epoch,
                            Wp2, wcnt2, rspw);
         return (int)hipGetLastError();
     }
+    stm_report_rider_launch(c, rest > 0 ? "k_upd_fw" : "k_upd_f", nfr, rest > 0 ? rest : 0, maxsl, 1, rest > 0 ? maxsl : 0);
     if (rest <= 0) return stm_launch_update_fused(c, flist, plist, nfr, 0, 1, maxsl, Wp, wpoff, wcnt, wflag, epoch, 1, st);
     hipLaunchKernelGGL(k_upd_fw, dim3(maxsl > rest ? maxsl : rest, maxsl > 2 ? maxsl : 2, 2 * nfr), dim3(NT), (size_t)stm_update_lds_bytes(),
                        st, c, flist, plist, nfr, maxsl, rest, Wp, wpoff, wcnt, wflag, epoch, Wp2, wcnt2);

@@ -98,6 +98,29 @@ def factorize(pkg, sym, Ap, Ai, Ax, tol, ntol, **options):
         pkg.set_options(**saved)
 
 
+def assert_same_bits(A, B):
+    """two downloads of one input's factors: the same bits in rank, rh_total, FIELDS and Stack[:rh_total]"""
+    assert (B.rank, B.rh_total) == (A.rank, A.rh_total)
+    for k in FIELDS:
+        assert np.array_equal(getattr(B, k), getattr(A, k)), k
+    assert np.array_equal(B.Stack[:B.rh_total], A.Stack[:A.rh_total])
+
+
+def assert_oracle(oracle, S, Ap, Ai, Ax, tol, n, stats, B):
+    """the factors B (with the stats of their factorization) against the CPU oracle, as test_gpu_column_step.py::check_against_oracle:
+    rank, staircase, Rdead and flops exact; Tau and the packed factors within 1e-11 of their 2-norms"""
+    No = oracle.factorize(S, Ap, Ai, Ax, tol, n)
+    assert B.rank == No.c.rank and B.rh_total == No.c.rh_total
+    np.testing.assert_array_equal(B.HStair[:S.rjsize], No.HStair[:S.rjsize])
+    np.testing.assert_array_equal(B.Rdead[:n], No.Rdead[:n])
+    assert stats["flops"] == No.c.flopcount
+    To, Fo = No.HTau[:S.rjsize], No.Stack[:No.c.rh_total]
+    dT, dF = np.linalg.norm(B.HTau[:S.rjsize] - To), np.linalg.norm(B.Stack[:B.rh_total] - Fo)
+    print(f"|dTau| {dT:.3e} / {max(np.linalg.norm(To), 1):.3e}   |dF| {dF:.3e} / {np.linalg.norm(Fo):.3e}")
+    assert dT <= 1e-11 * max(np.linalg.norm(To), 1)
+    assert dF <= 1e-11 * np.linalg.norm(Fo)
+
+
 def analyzed(pkg, fronts):
     """(sym, S, Ap, Ai, Ax) of diag(fronts) through the package's symbolic phase, columns in their given order: one front each"""
     Ap, Ai, Ax = block_diag_csc(fronts)

@@ -36,7 +36,8 @@ import importlib
 import numpy as np
 import pytest
 
-from block0_cases import B0_TIMELINE, DEAD_AT, FIELDS, analyzed, block0_count, factorize, make_front, riding_block0
+from block0_cases import (B0_TIMELINE, DEAD_AT, analyzed, assert_oracle, assert_same_bits, block0_count, factorize, make_front,
+                          riding_block0)
 
 pytestmark = pytest.mark.gpu
 M, FN = 600, 97
@@ -65,22 +66,8 @@ def check(pkg, oracle, monkeypatch, capfd, fronts, tol=-1.0, **options):
     print(f"block-0 workgroup sets: {ran} (expected {len(want)}: {want})")
     assert want and ran == len(want)
     assert st0["retries"] == 0 and st2["retries"] == 0 and st0["reschedules"] == 0 and st2["reschedules"] == 0
-    # ---- the serial kernels: the same bits ----
-    assert (B.rank, B.rh_total) == (A.rank, A.rh_total)
-    for k in FIELDS:
-        assert np.array_equal(getattr(B, k), getattr(A, k)), k
-    assert np.array_equal(B.Stack[:B.rh_total], A.Stack[:A.rh_total])
-    # ---- the CPU oracle (test_gpu_column_step.py::check_against_oracle) ----
-    No = oracle.factorize(S, Ap, Ai, Ax, tol, n)
-    assert B.rank == No.c.rank and B.rh_total == No.c.rh_total
-    np.testing.assert_array_equal(B.HStair[:S.rjsize], No.HStair[:S.rjsize])
-    np.testing.assert_array_equal(B.Rdead[:n], No.Rdead[:n])
-    assert st2["flops"] == No.c.flopcount
-    To, Fo = No.HTau[:S.rjsize], No.Stack[:No.c.rh_total]
-    dT, dF = np.linalg.norm(B.HTau[:S.rjsize] - To), np.linalg.norm(B.Stack[:B.rh_total] - Fo)
-    print(f"|dTau| {dT:.3e} / {max(np.linalg.norm(To), 1):.3e}   |dF| {dF:.3e} / {np.linalg.norm(Fo):.3e}")
-    assert dT <= 1e-11 * max(np.linalg.norm(To), 1)
-    assert dF <= 1e-11 * np.linalg.norm(Fo)
+    assert_same_bits(A, B)                                      # the serial kernels: the same bits
+    assert_oracle(oracle, S, Ap, Ai, Ax, tol, n, st2, B)         # the CPU oracle (test_gpu_column_step.py::check_against_oracle)
     return B
 
 
