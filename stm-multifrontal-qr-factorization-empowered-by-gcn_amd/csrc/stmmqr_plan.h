@@ -1,5 +1,9 @@
 // stmmqr_plan.h -- the plan object and the helpers shared by the host translation units of libstmmqr_hip.so (local to the library):
-//   stmmqr_host.cpp      device set-up, the symbolic plan, factorization entry points, download
+//   stmmqr_host.cpp      globals, options, device set-up and the side stream, device alloc / copy / free, shutdown
+//   stmmqr_planbuild.cpp the symbolic plan (build_plan), the pattern of A, plan create / destroy, stmmqr_plan_set_groups
+//   stmmqr_factorize.cpp the factorization driver: begin / group / finish / the whole call, around the pure recovery policy of
+//                        stmmqr_recover.h; its diagnostic prints in stmmqr_diag.cpp
+//   stmmqr_download.cpp  the factors out of the plan in the reference's layout (stmmqr_plan_download)
 //   stmmqr_schedule.cpp  arenas, the timeline allocator, the step timeline of every front group (stm_build_schedule)
 //   stmmqr_run.cpp       the step scheduler (stm_run_schedule: one step, serial, look-ahead, passengers), the pack pass
 //   stmmqr_multi.cpp     contribution blocks / panels in and out of a plan, shared fronts, the RCCL transport
@@ -30,6 +34,7 @@
 #include "stmmqr_kernels.h"
 #include "stmmqr_internal.h"
 #include "stmmqr_knobs.h"
+#include "stmmqr_recover.h"
 
 
 extern thread_local std::string g_err;
@@ -171,14 +176,9 @@ struct stmmqr_plan {
     long long rh_cap = 0;                // capacity of the R+H arena (doubles)
     long long rh_est_total = 0;          // all packed R+H blocks if no pivot column dies (symbolic; exact for full-rank input)
     std::vector<long long> rh_est_front; // ... per front (keepH = 0: the arena holds those of the fronts that do not keep their slab)
-    int rh_grow = 0;                     // 0: the arena is sized from that estimate; 1: from the hard bounds (it overflowed once)
     double rh_est_scale = 1.0;           // ... times STMMQR_RH_EST_SCALE, read once when the plan is created (tests shrink the estimate)
-    bool overflowed = false;             // a factorization did not fit the R+H arena at its hard bound: this plan does not recycle
     bool early_end = false;              // the schedule of group 0 stops every front at the panel where it is expected to run out of rows
-    bool full_schedule = false;          // ... it did not hold once (rank-deficient fronts): this plan schedules every panel from now on
-    bool early_phased = false;           // ... the caller of the phased interface asked for the cut schedule (stmmqr_plan_set_early_end)
-    bool early_end_failed = false;       // ... the last factorization found a front unfinished at its last scheduled panel
-    bool arena_overflow = false;         // the last factorization did not fit the arena (it is repeated with a larger one / without)
+    recover::State rec;                  // what the planner reads of earlier failures (arena growth, full schedule), the last finish's outcome
     std::vector<int> lists;              // host copy of d_lists
     int post_off = 0, rh_parts_off = 0, rh_maxparts = 1;
     long long farena = 0, carena = 0;
@@ -205,7 +205,6 @@ struct stmmqr_plan {
     DevBuf<int> d_wcnt, d_wcnt2;         // per column block of the update workspaces: slab tickets (zero between launches)
     DevBuf<int> d_wflag, d_wflag2;       // ... fused update: step + 1 once W2 of the column block is in its slot
     DevBuf<int> d_abort;                 // [1] a bounded wait ran out, [2] a front outlived its cut schedule, [3] a refused message
-    int abort2_before = 0;               // phased use: abort[2] as the groups run so far left it (reset_group puts it back)
     size_t wcnt_n = 1;
     DevBuf<long long> d_Rboff, d_total;
     DevBuf<long long> d_rhtop, d_fin;    // slab recycling: {bump pointer, overflow word}; Post-order offsets of the packed blocks
@@ -221,8 +220,6 @@ struct stmmqr_plan {
 
     // results of the last factorization
     bool factored = false, begun = false, first_group = true;
-    bool whole_call = false;             // inside stmmqr_factorize_device (which recovers the WHOLE factorization itself)
-    bool panel_wait_failed = false;      // a bounded inter-workgroup wait of a panel kernel ran out in the last factorization
     bool serial_panels = false;          // recovery: every panel by ONE workgroup (no inter-workgroup waits at all)
     long long rh_total = 0;
     long rank = 0;
@@ -300,5 +297,16 @@ int stm_run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req);
 int stm_run_pack(stmmqr_plan &P, bool &overflow);
 int stm_ensure_la_events(stmmqr_plan &P, size_t nsteps, const knobs::RunKnobs &k);
 int stm_ensure_device(int device);
+hipStream_t stm_side_stream_for(int device);                       // (stmmqr_host.cpp)
+void stm_destroy_side_streams();
+// stmmqr_planbuild.cpp
+int stm_set_pattern(stmmqr_plan &P, const stm_long *Ap, const stm_long *Ai);
 int stm_ensure_a_index(stmmqr_plan &P);
+// the diagnostic prints of stmmqr_factorize_finish, in the order it calls them (stmmqr_diag.cpp)
+void stm_diag_early_fronts(const stmmqr_plan &P);
+void stm_diag_dump_steps(const stmmqr_plan &P, const std::vector<float> &pair_ms);
+int stm_diag_panel_timeline(const stmmqr_plan &P, int dbg);
+int stm_diag_block0_launch(const stmmqr_plan &P, int dbg);
+int stm_diag_pipeline_counters(const stmmqr_plan &P, int dbg);
+void stm_diag_memdump(const stmmqr_plan &P);
 extern "C" int stm_check_c_slot(const stmmqr_plan &P, stm_long f, long long csize, const char *what);     // (defined inside the C ABI block)

@@ -227,7 +227,7 @@ struct Planner {
     {
         long long slabs = 0;
         for (long f = 0; f < nf; f++) slabs += (long long)P.fs[f].ld * P.fs[f].fn;
-        P.recycle = whole && !P.overflowed && k.recycles(slabs);
+        P.recycle = whole && !P.rec.overflowed && k.recycles(slabs);
     }
 
     void mark_pair_fronts()
@@ -264,11 +264,11 @@ struct Planner {
     // the device, but fm_est -- the rows if no pivot column dies -- is exact for a full-rank matrix: a plan that holds the whole tree
     // schedules floor(min(fm_est, fn) / 32) + 1 panels per front.  Should a front NOT be finished by its last scheduled panel
     // (pivot columns died below it: more rows reach it than estimated), k_cpack's extra workgroup raises abort[2] and the
-    // factorization is run again on the full schedule, which the plan then keeps (P.full_schedule; stats.retries counts it).
+    // factorization is run again on the full schedule, which the plan then keeps (P.rec.full_schedule; stats.retries counts it).
     // STMMQR_EARLY_END=0: every panel a step, as before. ----
     void cut_fronts()
     {
-        const bool early = (whole || P.early_phased) && !P.full_schedule && k.early_end;
+        const bool early = (whole || P.rec.early_phased) && !P.rec.full_schedule && k.early_end;
         for (long f = 0; f < nf; f++) {
             FrontSym &s = P.fs[f];
             s.nsched = s.npanels;
@@ -599,7 +599,7 @@ struct Planner {
             for (int i = 0; i < q; i++) kp[(size_t)bysize[(size_t)i]] = 1;
             const auto pk = timeline_offsets(P, kp, nstep, false);
             long long cap = hard_cap(kp);
-            if (!P.keep_h && !P.rh_grow) cap = std::min(cap, staged_est(kp));     // (R only: the arena follows the packed R)
+            if (!P.keep_h && !P.rec.rh_grow) cap = std::min(cap, staged_est(kp));     // (R only: the arena follows the packed R)
             const long long tot = pk.first + pk.second + cap;
             if (best < 0 || tot < best - best / 50) { best = tot; bestk = q; }      // (a kept front must buy at least 2 %)
         }
@@ -609,8 +609,8 @@ struct Planner {
         // (the estimate + 12.5 % where that is less: dead columns move rows into later fronts and can make the factors
         //  larger than the full-rank pattern says; an arena that overflows is regrown to the hard bound and the factorization
         //  repeated once -- stats.retries says so)
-        if (!P.rh_grow && !P.keep_h) P.rh_cap = std::max(1LL, std::min(P.rh_cap, staged_est(P.kept)));
-        else if (!P.rh_grow && P.rh_est_total > 0) {
+        if (!P.rec.rh_grow && !P.keep_h) P.rh_cap = std::max(1LL, std::min(P.rh_cap, staged_est(P.kept)));
+        else if (!P.rec.rh_grow && P.rh_est_total > 0) {
             // (P.rh_est_scale: tests shrink the estimate to drive the overflow path)
             const long long est = (long long)((double)P.rh_est_total * P.rh_est_scale);
             P.rh_cap = std::max(1LL, std::min(P.rh_cap, est + est / 8 + 4096));
