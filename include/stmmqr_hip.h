@@ -333,6 +333,10 @@ int stmmqr_transport_sendrecv(const stmmqr_transport *tr, const void *sendbuf, s
 /* off[0..fn]: start of each column of front f inside its packed R+H block (after stmmqr_factorize_finish) */
 int stmmqr_plan_front_rhoff(stmmqr_plan *plan, stm_long f, stm_long *off);
 
+/* slab recycling: 1 when front f keeps its slab (its packed block is produced on the fly by stmmqr_plan_download), 0 when its block
+ * is staged in the R+H arena; -1 for a plan that does not recycle its slabs or a bad f */
+int stmmqr_plan_front_kept(const stmmqr_plan *plan, stm_long f);
+
 /* device memory the plan holds right now, in bytes (what stmmqr_stats.device_bytes reports at the end of a factorization) */
 double stmmqr_plan_device_bytes(const stmmqr_plan *plan);
 
@@ -609,7 +613,9 @@ double stmmqr_last_seam_ms(void);
  * (device memory by purpose); STMMQR_DUMPSTEPS=file (detail runs: one line per step with what ran and how long); STMMQR_DBG (bit
  * mask, csrc/stmmqr_kernels.h; of general use: 16 diagnosis counters printed by stmmqr_factorize_finish -- panels by actual rows,
  * launched / useful update workgroups, refresh rounds --, 16384 no wave-pipelined panels: every short panel through the
- * multi-workgroup pipeline).  The Python package adds STMMQR_NATIVE_PHASES=0 and STMMQR_EARLY_END_SHARDED=0 (sharded.py: the
+ * multi-workgroup pipeline).  For tests of the download under slab recycling: STMMQR_DOWNLOAD_WIN (doubles per window of
+ * stmmqr_plan_download, read at every download; default 32 << 20 = 256 MB) and STMMQR_KEEP_FRONTS (0..3: that many of the largest
+ * fronts keep their slab, instead of the planner's choice; stmmqr_plan_front_kept tells which).  The Python package adds STMMQR_NATIVE_PHASES=0 and STMMQR_EARLY_END_SHARDED=0 (sharded.py: the
  * Python phase loop; the full schedule on sharded plans). */
 typedef struct stmmqr_options {
     int panel_width;        /* Householder panel width on device (<= 32); reference FCHUNK = 32                    */

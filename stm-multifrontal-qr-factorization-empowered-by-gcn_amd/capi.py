@@ -143,6 +143,7 @@ lib.stmmqr_plan_import_panel.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_voi
 lib.stmmqr_plan_export_front_cols.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, c_long_p]
 lib.stmmqr_plan_import_front_cols.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int]
 lib.stmmqr_plan_front_rhoff.argtypes = [C.c_void_p, C.c_long, c_long_p]
+lib.stmmqr_plan_front_kept.argtypes = [C.c_void_p, C.c_long]
 lib.stmmqr_plan_front_flops.argtypes = [C.c_void_p, C.c_long, c_double_p]
 lib.stmmqr_plan_device_bytes.argtypes = [C.c_void_p]
 lib.stmmqr_plan_device_bytes.restype = C.c_double
@@ -554,6 +555,10 @@ class HipQR:
         off = np.zeros(int(fn) + 1, I64)
         _check(lib.stmmqr_plan_front_rhoff(self._h, int(f), _ip(off)), "stmmqr_plan_front_rhoff")
         return off
+
+    def front_kept(self, f) -> int:
+        """1: front f keeps its slab under slab recycling, 0: its packed block is staged; -1: no recycling or a bad f"""
+        return int(lib.stmmqr_plan_front_kept(self._h, int(f)))
 
     def device_bytes(self) -> float:
         return float(lib.stmmqr_plan_device_bytes(self._h))

@@ -19,7 +19,7 @@ int stmmqr_plan_download(stmmqr_plan *plan, double *Stack, stm_long *Rblock_off,
     if (Stack && P.rh_total > 0 && P.recycle) {
         // slab recycling: the blocks lie in the arena in the order the fronts finished (kept fronts: still in front form); the
         // reference's layout is produced window by window in a bounce buffer (k_rh_window) and copied out, two windows in flight
-        const long long win = std::min<long long>(P.rh_total, 32LL << 20);            // 256 MB windows
+        const long long win = std::min<long long>(P.rh_total, knobs::num(knobs::K_DOWNLOAD_WIN));     // 256 MB windows (STMMQR_DOWNLOAD_WIN)
         if (P.d_bounce.n < (size_t)(2 * win)) LCHK(P.d_bounce.alloc((size_t)(2 * win)));
         const DevCtx c = P.ctx();
         const int parts = (int)std::min<long long>(64, std::max<long long>(1, win / (64 * 1024)));

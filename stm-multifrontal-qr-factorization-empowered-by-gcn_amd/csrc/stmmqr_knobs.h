@@ -50,7 +50,8 @@ enum When { PROCESS, PLAN, SCHED, RUN, CALL };
     X(PAIR_MIN, pair_min, long, INT, PLAIN, SCHED, 16384, "estimated rows from which a front takes the pair / quad update (options.pair_update)") \
     X(EARLY_END, early_end, bool, FLAG, PLAIN, SCHED, 1, "a front is scheduled up to the panel where it is expected to run out of rows (0: every panel a step)") \
     X(EARLY_SLACK, early_slack, int, INT, PLAIN, SCHED, 0, "... plus this many panels")                                             \
-    X(RIDE, ride, double, REAL, PLAIN, SCHED, 1.0, "envelope rule: factor on the height a riding front may have")
+    X(RIDE, ride, double, REAL, PLAIN, SCHED, 1.0, "envelope rule: factor on the height a riding front may have")            \
+    X(KEEP_FRONTS, keep_fronts, int, INT, PLAIN, SCHED, -1, "slab recycling: how many of the largest fronts keep their slab (0..3, larger reads as 3; -1: the planner chooses) -- tests force the set that the download packs on the fly")
 #define STM_KNOBS_RUN(X)                                                                                                            \
     X(LA_MIN, la_min, long, INT, PLAIN, RUN, 2500, "look-ahead: tiles (256 x 32) of update beyond block 0 from which a step goes to the side stream (two cross-stream hand-offs, ~25 us)") \
     X(LA_MIN_FUSED, la_min_fused, long, INT, PLAIN, RUN, 1500, "... where T + block 0 is one fused launch")                         \
@@ -72,6 +73,7 @@ enum When { PROCESS, PLAN, SCHED, RUN, CALL };
     X(RESIDENT_CACHE, resident_cache, int, INT, BOOLEAN, CALL, -1, "recycled slabs: the scratch holds every front in front form (1) or one tree level (0); unset: by free memory") \
     X(NULL_SLAB, null_slab, long, INT, MIN1, CALL, 2048, "rows of the null-space basis N per slab of the Gram matrix N'N and of N'X: a workgroup per (tile, slab), the partial sums added in slab order (read when N is built and at every projection)") \
     X(CHUNK, chunk, int, INT, PLAIN, CALL, 1, "fronts per panel launch with STMMQR_DBG bit 9")                                      \
+    X(DOWNLOAD_WIN, download_win, long, INT, POSITIVE, CALL, 32L << 20, "doubles per window of stmmqr_plan_download on a plan that recycles its slabs (256 MB; tests shrink it to put window edges where they want them)") \
     X(PLAN_CACHE, plan_cache, int, INT, MIN0, CALL, 1, "plans the drop-in seam keeps (0: no cache)")                                \
     X(SEAM_EARLY_ALLOC, seam_early_alloc, int, INT, PLAIN, CALL, 1, "the seam populates the returned stack beside the factorization: 0 never, 1 for cached plans, 2 for first calls too") \
     X(SEAM_TIMING, seam_timing, bool, FLAG, PRESENT, CALL, 0, "the seam prints where a call spent its time")                        \

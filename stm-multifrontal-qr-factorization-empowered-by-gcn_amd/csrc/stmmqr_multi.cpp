@@ -692,6 +692,14 @@ int stmmqr_plan_front_rhoff(stmmqr_plan *plan, stm_long f, stm_long *off)
     return 0;
 }
 
+/* slab recycling: 1 front f keeps its slab (its block is packed on the fly by the download), 0 its block is staged in the R+H
+   arena; -1 the plan does not recycle, or a bad f */
+int stmmqr_plan_front_kept(const stmmqr_plan *plan, stm_long f)
+{
+    if (!plan || !plan->recycle || f < 0 || f >= plan->nf || (size_t)f >= plan->kept.size()) return -1;
+    return plan->kept[(size_t)f] ? 1 : 0;
+}
+
 /* device memory held by the plan right now (bytes): arenas, factors, workspaces, index arrays */
 double stmmqr_plan_device_bytes(const stmmqr_plan *plan) { return plan ? plan->device_bytes() : 0.0; }
 

@@ -594,7 +594,10 @@ struct Planner {
         };
         long long best = -1;
         int bestk = 0;
-        for (int q = 0; q <= std::min(3L, nf); q++) {
+        // (STMMQR_KEEP_FRONTS: tests force how many keep it; everything after the choice runs on the forced set)
+        const int forced = (k.keep_fronts >= 0) ? (int)std::min<long>(std::min(k.keep_fronts, 3), nf) : -1;
+        if (forced >= 0) bestk = forced;
+        for (int q = 0; forced < 0 && q <= std::min(3L, nf); q++) {
             std::vector<char> kp((size_t)std::max(1L, nf), 0);
             for (int i = 0; i < q; i++) kp[(size_t)bysize[(size_t)i]] = 1;
             const auto pk = timeline_offsets(P, kp, nstep, false);

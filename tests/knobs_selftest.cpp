@@ -74,6 +74,27 @@ int main()
     setenv("STMMQR_MEMDUMP", "", 1);
     CHECK(on(K_MEMDUMP), "MEMDUMP set to the empty text is on");
     clear_all();
+    // the window of the download and the forced kept set
+    CHECK(num(K_DOWNLOAD_WIN) == (32L << 20), "DOWNLOAD_WIN unset reads %ld", num(K_DOWNLOAD_WIN));
+    for (const char *s : {"0", "-5", "text"}) {
+        setenv("STMMQR_DOWNLOAD_WIN", s, 1);
+        CHECK(num(K_DOWNLOAD_WIN) == (32L << 20), "DOWNLOAD_WIN=%s reads %ld, not the default", s, num(K_DOWNLOAD_WIN));
+    }
+    setenv("STMMQR_DOWNLOAD_WIN", "4096", 1);
+    CHECK(num(K_DOWNLOAD_WIN) == 4096, "DOWNLOAD_WIN=4096 reads %ld", num(K_DOWNLOAD_WIN));
+    CHECK(TABLE[K_DOWNLOAD_WIN].when == CALL && TABLE[K_DOWNLOAD_WIN].rule == POSITIVE, "DOWNLOAD_WIN: read at every download");
+    CHECK(num(K_KEEP_FRONTS) == -1 && BuildKnobs::read().keep_fronts == -1, "KEEP_FRONTS unset: the planner chooses");
+    setenv("STMMQR_KEEP_FRONTS", "0", 1);
+    CHECK(num(K_KEEP_FRONTS) == 0 && BuildKnobs::read().keep_fronts == 0, "KEEP_FRONTS=0 reads %ld", num(K_KEEP_FRONTS));
+    CHECK(TABLE[K_KEEP_FRONTS].when == SCHED && TABLE[K_KEEP_FRONTS].rule == PLAIN, "KEEP_FRONTS: read when a schedule is built");
+    {
+        // neither row is in the key of a captured graph
+        clear_all();
+        const unsigned long long k0 = RunKnobs::read().key();
+        setenv("STMMQR_DOWNLOAD_WIN", "4096", 1); setenv("STMMQR_KEEP_FRONTS", "2", 1);
+        CHECK(RunKnobs::read().key() == k0, "DOWNLOAD_WIN / KEEP_FRONTS move the key of the captured graph");
+    }
+    clear_all();
     const long long small = 1 << 20, large = 32LL << 20;
     CHECK(!BuildKnobs::read().recycles(small) && BuildKnobs::read().recycles(large), "RECYCLE unset: by size");
     setenv("STMMQR_RECYCLE", "1", 1);

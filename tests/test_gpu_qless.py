@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from pack_window_cases import front_walk
 from stmmqr_testlib import EPS, Symbolic, cond_probe, load_golden, numeric_from_gpu, scalar, solve_tol
 
 pytestmark = pytest.mark.gpu
@@ -61,22 +62,11 @@ def r_only_blocks(S, N):
         stair = N.HStair[p1:p1 + fn]
         src = N.Stack[int(N.Rblock_off[f]):]
         blk = []
-        if fm > 0 and fn > 0:
-            rm, at = 0, 0
-            for k in range(fp):                          # R+H column k: t entries (t = rm for a dead column), R = the first rm
-                t = int(stair[k])
-                if t == 0:
-                    t = rm
-                elif rm < fm:
-                    rm += 1
-                blk.append(src[at:at + rm])
-                at += t
-            h = rm
-            for k in range(fp, fn):                      # rm entries of R, then the H rows h .. t-1
-                t = int(stair[k])
-                h = min(h + 1, fm)
-                blk.append(src[at:at + rm])
-                at += rm + max(t - h, 0)
+        rm_k, clen = front_walk(stair, fp, fn, fm)      # R+H column k: clen[k] entries, R = the first rm_k[k]
+        at = 0
+        for k in range(fn if fm > 0 else 0):
+            blk.append(src[at:at + int(rm_k[k])])
+            at += int(clen[k])
         out.append(np.concatenate(blk) if blk else np.zeros(0))
     return out
 

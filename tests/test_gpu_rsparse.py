@@ -12,6 +12,7 @@ import importlib
 import numpy as np
 import pytest
 
+from pack_window_cases import front_walk
 from stmmqr_testlib import Symbolic, load_golden, scalar
 from test_refactor_cpu import full_matrix, new_values
 
@@ -182,22 +183,12 @@ def stored_and_zero(S, N):
         p = int(N.Rblock_off[f])
         fp, pr = int(S.Super[f + 1] - S.Super[f]), int(S.Rp[f])
         fn, fm = int(S.Rp[f + 1]) - pr, int(N.Hm[f])
-        rm = h = 0
+        rm_k, clen = front_walk(N.HStair[pr:pr + fn], fp, fn, fm)      # column k: clen[k] entries, the first rm_k[k] are R's
         for k in range(fn):
-            t = int(N.HStair[pr + k])
-            if k < fp:
-                if t == 0:
-                    t = rm
-                elif rm < fm:
-                    rm += 1
-                h = rm
-            else:
-                h = min(h + 1, fm)
+            rm = int(rm_k[k])
             stored += rm
             zeros += int(np.count_nonzero(N.Stack[p:p + rm] == 0.0))
-            p += rm
-            if t >= h:
-                p += t - h
+            p += int(clen[k])
     return stored, zeros
 
 
