@@ -33,6 +33,13 @@ struct FrontSym {
                              // are split over workgroups (k_rtbig_*) -- k_rtsolve cannot hold it in LDS, or STMMQR_RTBIG_MIN (plan time)
 };
 
+// host side only: a tree level of a front group, as the planner lists it (stmmqr_sched.h) and the solve / Q-apply launchers walk it
+// (stmmqr_restables.h); offsets into the schedule's lists
+struct Level {
+    int all_off = 0, n_all = 0;          // every front of the level (small first, then big by npanels desc)
+    int n_small = 0, n_big = 0;
+};
+
 // one pending block reflector (written by the panel kernel, read by the update kernel)
 #define STM_PD_RING 4                                           // panel descriptions and T factors kept per front
 #define STM_PDI(p) ((p) & (STM_PD_RING - 1))

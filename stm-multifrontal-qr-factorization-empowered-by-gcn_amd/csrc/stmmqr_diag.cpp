@@ -11,7 +11,7 @@ void stm_diag_early_fronts(const stmmqr_plan &P)
     for (long f = 0; f < P.nf; f++) {
         if (P.group[f] < 0) continue;                  // factorized elsewhere
         const FrontNum &nm = P.h_fnum[f];
-        const FrontSym &s = P.fs[f];
+        const FrontSym &s = P.sch.fs[f];
         if (s.nsched < s.npanels && (!nm.done || nm.g < std::min(nm.fm, s.fn)))
             fprintf(stderr, "[early] front %ld fn %d fp %d fm %d fm_est %d fm_ub %d g %d rank %d done %d nsched %d npanels %d\n", f, s.fn, s.fp, nm.fm, s.fm_est,
                     s.fm_ub, nm.g, nm.rank, nm.done, s.nsched, s.npanels);
@@ -25,21 +25,21 @@ void stm_diag_dump_steps(const stmmqr_plan &P, const std::vector<float> &pair_ms
     FILE *dump = (!pair_ms.empty() && knobs::text(knobs::K_DUMPSTEPS)) ? fopen(knobs::text(knobs::K_DUMPSTEPS), "w") : nullptr;
     if (!dump) return;
     std::vector<float> st_panel, st_upd;
-    if (!P.gsteps.empty()) { st_panel.assign(P.gsteps[0].size(), 0.f); st_upd.assign(P.gsteps[0].size(), 0.f); }
+    if (!P.sch.gsteps.empty()) { st_panel.assign(P.sch.gsteps[0].size(), 0.f); st_upd.assign(P.sch.gsteps[0].size(), 0.f); }
     for (size_t q = 0; q < pair_ms.size(); q++) {
         if ((size_t)P.evpairs[q].step >= st_panel.size()) continue;
         if (P.evpairs[q].cat == 2) st_panel[(size_t)P.evpairs[q].step] += pair_ms[q];
         if (P.evpairs[q].cat == 3) st_upd[(size_t)P.evpairs[q].step] += pair_ms[q];
     }
     for (size_t t = 0; t < st_panel.size(); t++) {
-        const Step &S = P.gsteps[0][t];
+        const Step &S = P.sch.gsteps[0][t];
         int maxrows = 0, pwg = 0;
         long tiles = 0;
         for (int i = 0; i < S.n_act; i++) {
-            const FrontSym &fsym = P.fs[P.lists[S.act_off + i]];
-            const int p = P.lists[S.plist_off + i];
+            const FrontSym &fsym = P.sch.fs[P.sch.lists[S.act_off + i]];
+            const int p = P.sch.lists[S.plist_off + i];
             maxrows = std::max(maxrows, stm_panel_rows_est(fsym, p));
-            pwg += stm_use_ca(fsym, p, P.plan_algo, P.ca_min) ? stm_ca_slabs(fsym) : stm_tall_launches(fsym, p, P.tall_min);
+            pwg += stm_use_ca(fsym, p, P.sch.plan_algo, P.sch.ca_min) ? stm_ca_slabs(fsym) : stm_tall_launches(fsym, p, P.sch.tall_min);
             tiles += (long)stm_upd_ncb(fsym, p) * stm_upd_nsl(fsym);
         }
         fprintf(dump, "%zu n_act %d maxrows %d nsub %d pwg %d nca_use %d maxcb %d maxsl %d split %d tiles %ld panel_us %.1f upd_us %.1f\n", t,
@@ -112,5 +112,5 @@ void stm_diag_memdump(const stmmqr_plan &P)
                     "kept T %.3f  pair -Y %.3f  Sx/Ax/smap %.3f  per-column arrays %.3f  total %.3f  (recycle %d, kept fronts %d, maxstack %.3f)\n",
             gb(P.d_F), gb(P.d_C), gb(P.d_RH), gb(P.d_Wp), gb(P.d_Wp2), gb(P.d_Tall), gb(P.d_Ypend), gb(P.d_Sx) + gb(P.d_Ax) + gb(P.d_smap),
             gb(P.d_Stair) + gb(P.d_Tau) + gb(P.d_Hii) + gb(P.d_Cmap) + gb(P.d_Cursor) + gb(P.d_Rhoff) + gb(P.d_Rjrel) + gb(P.d_Sjrel),
-            P.stats.device_bytes * 1e-9, (int)P.recycle, (int)std::count(P.kept.begin(), P.kept.end(), (char)1), 8e-9 * (double)P.maxstack);
+            P.stats.device_bytes * 1e-9, (int)P.sch.recycle, (int)std::count(P.sch.kept.begin(), P.sch.kept.end(), (char)1), 8e-9 * (double)P.maxstack);
 }

@@ -16,7 +16,7 @@ int stmmqr_plan_download(stmmqr_plan *plan, double *Stack, stm_long *Rblock_off,
     hipStream_t st = P.stream;
     const long nf = P.nf, m = P.m, n = P.n;
     HIPCHK(hipEventRecord(P.ev[6], st));
-    if (Stack && P.rh_total > 0 && P.recycle) {
+    if (Stack && P.rh_total > 0 && P.sch.recycle) {
         // slab recycling: the blocks lie in the arena in the order the fronts finished (kept fronts: still in front form); the
         // reference's layout is produced window by window in a bounce buffer (k_rh_window) and copied out, two windows in flight
         const long long win = std::min<long long>(P.rh_total, knobs::num(knobs::K_DOWNLOAD_WIN));     // 256 MB windows (STMMQR_DOWNLOAD_WIN)
@@ -30,8 +30,8 @@ int stmmqr_plan_download(stmmqr_plan *plan, double *Stack, stm_long *Rblock_off,
             const long long w1 = std::min(P.rh_total, w0 + win);
             double *out = P.d_bounce.p + (i & 1) * win;
             if (i >= 2 && hipEventSynchronize(evw[i & 1]) != hipSuccess) rc = 1;       // (the copy that last read this half is done)
-            if (!rc && (P.keep_h ? stm_launch_rh_window(c, P.d_lists.p + P.own_off, P.n_own, parts, P.d_fin.p, P.d_kept.p, P.d_RH.p, w0, w1, out, st)
-                                 : stm_launch_r_window(c, P.d_lists.p + P.own_off, P.n_own, parts, P.d_fin.p, P.d_kept.p, P.d_RH.p, w0, w1, out, st)))
+            if (!rc && (P.keep_h ? stm_launch_rh_window(c, P.d_lists.p + P.sch.own_off, P.sch.n_own, parts, P.d_fin.p, P.d_kept.p, P.d_RH.p, w0, w1, out, st)
+                                 : stm_launch_r_window(c, P.d_lists.p + P.sch.own_off, P.sch.n_own, parts, P.d_fin.p, P.d_kept.p, P.d_RH.p, w0, w1, out, st)))
                 rc = 1;
             if (!rc && hipMemcpyAsync(Stack + w0, out, (size_t)(w1 - w0) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) rc = 1;
             if (!rc && hipEventRecord(evw[i & 1], st) != hipSuccess) rc = 1;
@@ -51,7 +51,7 @@ int stmmqr_plan_download(stmmqr_plan *plan, double *Stack, stm_long *Rblock_off,
         HIPCHK(hipMemcpyAsync(HTau, P.d_Tau.p, (size_t)P.rjsize * sizeof(double), hipMemcpyDeviceToHost, st));
     if (Rdead && n > 0) HIPCHK(hipMemcpyAsync(Rdead, P.d_Rdead.p, (size_t)n, hipMemcpyDeviceToHost, st));
     if (nf > 0)
-        HIPCHK(hipMemcpyAsync(rboff.data(), P.recycle ? P.d_fin.p : P.d_Rboff.p, (size_t)nf * sizeof(long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(rboff.data(), P.sch.recycle ? P.d_fin.p : P.d_Rboff.p, (size_t)nf * sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipEventRecord(P.ev[7], st));
     HIPCHK(hipStreamSynchronize(st));
     float ms = 0;
@@ -93,7 +93,7 @@ int stmmqr_plan_download(stmmqr_plan *plan, double *Stack, stm_long *Rblock_off,
             const FrontNum &nm = P.h_fnum[f];
             const long rm = nm.rank, fm = nm.fm;
             for (long i = 0; i < rm; i++) W[Hi[i]] = row1++;
-            const long cn = P.fs[f].fn - P.fs[f].fp;
+            const long cn = P.sch.fs[f].fn - P.sch.fs[f].fp;
             const long cm = std::min(fm - rm, cn);
             for (long i = fm - 1; i >= rm + cm; i--) W[Hi[i]] = --row2;
         }

@@ -20,7 +20,7 @@ int reset_factorization(stmmqr_plan &P)
     hipStream_t st = P.stream;
     LCHK(stm_ensure_arenas(P));
     // (with slab recycling every front's slab is zeroed when the front starts: k_zero_slabs in prep)
-    if (!P.recycle) HIPCHK(hipMemsetAsync(P.d_F.p, 0, (size_t)P.farena * sizeof(double), st));
+    if (!P.sch.recycle) HIPCHK(hipMemsetAsync(P.d_F.p, 0, (size_t)P.sch.farena * sizeof(double), st));
     HIPCHK(hipMemsetAsync(P.d_rhtop.p, 0, 2 * sizeof(long long), st));
     HIPCHK(hipMemsetAsync(P.d_Rdead.p, 0, (size_t)std::max(1L, P.n), st));
     HIPCHK(hipMemsetAsync(P.d_fnum.p, 0, (size_t)std::max(1L, P.nf) * sizeof(FrontNum), st));
@@ -44,7 +44,7 @@ int reset_group(stmmqr_plan &P, int grp)
     const FrontNum zero = FrontNum();
     for (long f = 0; f < P.nf; f++) {
         if (P.group[f] != grp) continue;
-        const FrontSym &s = P.fs[f];
+        const FrontSym &s = P.sch.fs[f];
         HIPCHK(hipMemsetAsync(P.d_F.p + s.foff, 0, (size_t)s.ld * (size_t)s.fn * sizeof(double), st));
         HIPCHK(hipMemcpyAsync(P.d_fnum.p + f, &zero, sizeof zero, hipMemcpyHostToDevice, st));
         if (s.fp > 0) HIPCHK(hipMemsetAsync(P.d_Rdead.p + s.col1, 0, (size_t)s.fp, st));
@@ -61,7 +61,7 @@ int reset_group(stmmqr_plan &P, int grp)
     // slab recycling: a recycling plan holds the whole tree in this one group, and the aborted attempt has staged packed blocks behind
     // the arena's bump pointer; the rerun stages every block again, so the pointer (and the overflow word) go back to zero -- otherwise
     // the second set lands behind the first and overflows an arena that holds the estimate + 12.5 %
-    if (P.recycle) HIPCHK(hipMemsetAsync(P.d_rhtop.p, 0, 2 * sizeof(long long), st));
+    if (P.sch.recycle) HIPCHK(hipMemsetAsync(P.d_rhtop.p, 0, 2 * sizeof(long long), st));
     HIPCHK(hipStreamSynchronize(st));                       // (`zero` lives on this stack frame)
     return 0;
 }
@@ -90,7 +90,7 @@ int factorize_begin(stmmqr_plan *plan, const stm_long *Ap, const stm_long *Ai, c
             if (P.group[f] != 0) return fail(STMMQR_ERR_INVALID, "a plan without H (keepH = 0) takes one group only");
     // phased use (begin / group / finish by the caller) has no loop around the factorization: what the last finish asked of the
     // schedule happens here (the whole call has acted on it in its own loop)
-    if (!whole_call && recover::at_phased_begin(P.rec, P.early_end, P.recycle) == Action::REBUILD) PASS(rebuild_schedule(P));
+    if (!whole_call && recover::at_phased_begin(P.rec, P.sch.early_end, P.sch.recycle) == Action::REBUILD) PASS(rebuild_schedule(P));
     P.rec.last = Outcome::DONE;
     const double host_ms_plan = P.stats.ms_host;
     P.stats = stmmqr_stats();
@@ -115,7 +115,7 @@ int factorize_begin(stmmqr_plan *plan, const stm_long *Ap, const stm_long *Ai, c
 
 // The step schedule of group 0 as a hipGraph, captured once per plan and per everything that travels in the kernel arguments or
 // decides what is launched: (tol, ntol, debug mask), the schedule generation (set_groups rebuilds the lists and may move the
-// workspaces) and the run-time options.  On return P.graph_exec is the graph to launch and the host statistics of one run of the
+// workspaces) and the run-time options.  On return P.graph.exec is the graph to launch and the host statistics of one run of the
 // schedule are added (by the capture itself, or from what the capture counted).
 int ensure_graph(stmmqr_plan &P)
 {
@@ -127,21 +127,20 @@ int ensure_graph(stmmqr_plan &P)
     for (long long v : {(long long)g_opt.lookahead, (long long)g_opt.split_update, (long long)g_opt.fused_update, (long long)g_opt.pair_update,
                         (long long)P.serial_panels, (long long)c.tune, (long long)P.keep_h})
         optkey = knobs::fold(optkey, (unsigned long long)v);
-    if (P.graph_exec && P.graph_tol == c.tol && P.graph_ntol == c.ntol && P.graph_dbg == c.dbg && P.graph_gen == P.sched_gen &&
-        P.graph_opt == optkey) {
+    const stmmqr_plan::Graph::Key key{c.tol, c.ntol, c.dbg, optkey, P.sched_gen};
+    if (P.graph.exec && P.graph.key == key) {
         // (the statistics stm_run_schedule accumulates on the host)
-        P.stats.nlaunch += P.graph_nlaunch;
-        P.stats.nlevels += (long)P.glevels[0].size();
-        P.stats.nsteps += (long)P.gsteps[0].size();
+        P.stats.nlaunch += P.graph.nlaunch;
+        P.stats.nlevels += (long)P.sch.glevels[0].size();
+        P.stats.nsteps += (long)P.sch.gsteps[0].size();
         return 0;
     }
-    if (P.graph_exec) { (void)hipGraphExecDestroy(P.graph_exec); P.graph_exec = nullptr; }
-    P.graph_nlaunch = 0;
+    P.graph.clear();
     // everything stm_run_schedule creates lazily is created BEFORE the capture: the device's side stream (device
     // properties, a CU-masked stream, an atexit handler) and the per-step events of the look-ahead
-    if (g_opt.lookahead && !P.serial_panels && P.gsteps[0].size() > 1) {
+    if (g_opt.lookahead && !P.serial_panels && P.sch.gsteps[0].size() > 1) {
         if (!P.side) P.side = stm_side_stream_for(P.device);
-        PASS(stm_ensure_la_events(P, P.gsteps[0].size(), rk));
+        PASS(stm_ensure_la_events(P, P.sch.gsteps[0].size(), rk));
     }
     const long nl0 = P.stats.nlaunch;
     hipGraph_t gph = nullptr;
@@ -154,10 +153,10 @@ int ensure_graph(stmmqr_plan &P)
     const hipError_t ce = hipStreamEndCapture(P.stream, &gph);
     if (e) { if (gph) (void)hipGraphDestroy(gph); return e; }
     HIPCHK(ce);
-    HIPCHK(hipGraphInstantiate(&P.graph_exec, gph, nullptr, nullptr, 0));
+    HIPCHK(hipGraphInstantiate(&P.graph.exec, gph, nullptr, nullptr, 0));
     (void)hipGraphDestroy(gph);
-    P.graph_tol = c.tol; P.graph_ntol = c.ntol; P.graph_dbg = c.dbg; P.graph_gen = P.sched_gen; P.graph_opt = optkey;
-    P.graph_nlaunch = P.stats.nlaunch - nl0;
+    P.graph.key = key;
+    P.graph.nlaunch = P.stats.nlaunch - nl0;
     return 0;
 }
 
@@ -171,7 +170,7 @@ int factorize_group(stmmqr_plan *plan, int group, int detail, bool whole_call)
     int e = 0;
     if (graph_ok) {
         PASS(ensure_graph(P));
-        HIPCHK(hipGraphLaunch(P.graph_exec, P.stream));
+        HIPCHK(hipGraphLaunch(P.graph.exec, P.stream));
     } else
         e = stm_run_schedule(P, detail != 0, group, nullptr);
     // Phased use (begin / group / finish called by the host: the sharded path): a bounded panel wait that ran out is found
@@ -271,10 +270,10 @@ void sums_over_fronts(stmmqr_plan &P)
     for (long f = 0; f < P.nf; f++) {
         if (P.group[f] < 0) continue;                  // factorized elsewhere
         const FrontNum &nm = P.h_fnum[f];
-        const FrontSym &s = P.fs[f];
+        const FrontSym &s = P.sch.fs[f];
         flops += nm.flops;
         fl_upd += nm.flops_upd;
-        if ((size_t)f < P.pair_front.size() && P.pair_front[f]) fl_upd_pair += nm.flops_upd;
+        if ((size_t)f < P.sch.pair_front.size() && P.sch.pair_front[f]) fl_upd_pair += nm.flops_upd;
         rank += nm.rank;
         const double cn = s.fn - s.fp, cm = nm.cm;
         const double csize = cm * (cm + 1) / 2 + cm * (cn - cm);
@@ -348,10 +347,10 @@ int stmmqr_factorize_device(stmmqr_plan *plan, const stm_long *Ap, const stm_lon
         int e = factorize_begin(plan, Ap, Ai, Ax, ax_on_device, tol, ntol, true);
         if (!e) plan->stats.retries = w.retries();               // (visible in stmmqr_stats: bench.py asserts 0)
         if (!e) plan->stats.reschedules = w.reschedules;
-        for (int g = 0; g < (int)plan->glevels.size() && !e; g++) e = factorize_group(plan, g, detail, true);
+        for (int g = 0; g < (int)plan->sch.glevels.size() && !e; g++) e = factorize_group(plan, g, detail, true);
         Outcome o = Outcome::DONE;
         if (!e && (e = stmmqr_factorize_finish(plan, stats)) != 0) o = plan->rec.last;
-        const Action a = recover::after_pass(plan->rec, w, o, plan->recycle);
+        const Action a = recover::after_pass(plan->rec, w, o, plan->sch.recycle);
         plan->serial_panels = false;                 // (also before a rebuild, which reads it nowhere: the next pass sets it anew)
         if (a == Action::RETURN) return e;
         if (g_opt.verbose) {

@@ -6,7 +6,7 @@
 // next call to see the new value.
 //   PROCESS  once per process, at the first use (knobs::once<K_...>())
 //   PLAN     when a plan is created (build_plan)
-//   SCHED    at every build of a schedule (BuildKnobs::read at the top of stm_build_schedule; the plan's sched_gen covers them)
+//   SCHED    at every build of a schedule (BuildKnobs::read where a schedule is about to be built: sched::Inputs::k; the plan's sched_gen covers them)
 //   RUN      at every run of a schedule (RunKnobs::read at the top of stm_run_schedule; RunKnobs::key is what a captured hipGraph is
 //            keyed by: a RUN row is a field of RunKnobs, so the run cannot read a knob that the key forgets)
 //   CALL     at every call of the function that uses it
@@ -134,7 +134,7 @@ inline unsigned long long fold(unsigned long long h, double v)
     return fold(h, b);
 }
 
-// what stm_build_schedule reads of the environment, once at its top
+// what a build of the schedule (sched::build, stmmqr_sched.h) reads of the environment: read once by its caller
 struct BuildKnobs {
 #define X(NAME, field, ctype, ...) ctype field;
     STM_KNOBS_SCHED(X)

@@ -14,9 +14,9 @@ int stmmqr_plan_front_info(stmmqr_plan *plan, stm_long f, stm_long *info)
     HIPCHK(hipStreamSynchronize(P.stream));
     FrontNum nm;
     HIPCHK(hipMemcpy(&nm, P.d_fnum.p + f, sizeof nm, hipMemcpyDeviceToHost));
-    const long cn = P.fs[f].fn - P.fs[f].fp, cm = nm.cm;
+    const long cn = P.sch.fs[f].fn - P.sch.fs[f].fp, cm = nm.cm;
     info[0] = nm.fm; info[1] = nm.rank; info[2] = cm; info[3] = cm * (cm + 1) / 2 + cm * (cn - cm);
-    info[4] = P.fs[f].fn; info[5] = P.fs[f].fp;
+    info[4] = P.sch.fs[f].fn; info[5] = P.sch.fs[f].fp;
     return 0;
 }
 
@@ -29,7 +29,7 @@ int stmmqr_plan_export_front(stmmqr_plan *plan, stm_long f, double *C, stm_long 
     stmmqr_plan &P = *plan;
     if ((e = stm_check_c_slot(P, f, info[3], "stmmqr_plan_export_front"))) return e;
     if (info[3] > 0 && C) {
-        HIPCHK(hipMemcpy(C, P.d_C.p + P.fs[f].coff, (size_t)info[3] * sizeof(double),
+        HIPCHK(hipMemcpy(C, P.d_C.p + P.sch.fs[f].coff, (size_t)info[3] * sizeof(double),
                          c_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
         // (a device-to-device hipMemcpy may return before the copy has run, and the plans' streams are non-blocking: they are not
         //  ordered behind the null stream.  The block is complete when this call returns, whatever stream reads it next.)
@@ -37,7 +37,7 @@ int stmmqr_plan_export_front(stmmqr_plan *plan, stm_long f, double *C, stm_long 
     }
     if (info[2] > 0 && rows) {
         std::vector<int> r32((size_t)info[2]);
-        HIPCHK(hipMemcpy(r32.data(), P.d_Hii.p + P.fs[f].hip + info[1], (size_t)info[2] * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(r32.data(), P.d_Hii.p + P.sch.fs[f].hip + info[1], (size_t)info[2] * sizeof(int), hipMemcpyDeviceToHost));
         for (long i = 0; i < info[2]; i++) rows[i] = r32[i];
     }
     return 0;
@@ -50,8 +50,8 @@ int stmmqr_plan_import_front(stmmqr_plan *plan, stm_long f, stm_long fm, stm_lon
     if (!plan || f < 0 || f >= plan->nf) return fail(STMMQR_ERR_INVALID, "bad front");
     stmmqr_plan &P = *plan;
     HIPCHK(hipSetDevice(P.device));
-    const long cn = P.fs[f].fn - P.fs[f].fp;
-    if (cm < 0 || cm > cn || rank < 0 || rank + cm > P.fs[f].fm_ub)
+    const long cn = P.sch.fs[f].fn - P.sch.fs[f].fp;
+    if (cm < 0 || cm > cn || rank < 0 || rank + cm > P.sch.fs[f].fm_ub)
         return fail(STMMQR_ERR_INVALID, "imported front does not fit the symbolic bounds");
     const long csize = cm * (cm + 1) / 2 + cm * (cn - cm);
     if (!P.begun) return fail(STMMQR_ERR_INVALID, "stmmqr_plan_import_front outside factorize_begin / factorize_finish (begin resets every front's state)");
@@ -63,7 +63,7 @@ int stmmqr_plan_import_front(stmmqr_plan *plan, stm_long f, stm_long fm, stm_lon
     nm.fm = (int)fm; nm.rank = (int)rank; nm.cm = (int)cm; nm.done = 1; nm.g = (int)rank;
     HIPCHK(hipMemcpy(P.d_fnum.p + f, &nm, sizeof nm, hipMemcpyHostToDevice));
     if (csize > 0) {
-        HIPCHK(hipMemcpy(P.d_C.p + P.fs[f].coff, C, (size_t)csize * sizeof(double),
+        HIPCHK(hipMemcpy(P.d_C.p + P.sch.fs[f].coff, C, (size_t)csize * sizeof(double),
                          c_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
         // (device to device: the copy is enqueued on the null stream and the call may return before it has run; the parent's
         //  assembly reads the block on the plan's non-blocking stream, which does not wait for the null stream -- wait here)
@@ -72,7 +72,7 @@ int stmmqr_plan_import_front(stmmqr_plan *plan, stm_long f, stm_long fm, stm_lon
     if (cm > 0) {
         std::vector<int> r32((size_t)cm);
         for (long i = 0; i < cm; i++) r32[i] = (int)rows[i];
-        HIPCHK(hipMemcpy(P.d_Hii.p + P.fs[f].hip + rank, r32.data(), (size_t)cm * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(P.d_Hii.p + P.sch.fs[f].hip + rank, r32.data(), (size_t)cm * sizeof(int), hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -84,8 +84,8 @@ int stmmqr_plan_import_front(stmmqr_plan *plan, stm_long f, stm_long fm, stm_lon
 // front, the factorized panel. ----
 int stmmqr_plan_group_steps(stmmqr_plan *plan, int group)
 {
-    if (!plan || group < 0 || group >= (int)plan->gsteps.size()) { fail(STMMQR_ERR_INVALID, "no such front group"); return -1; }
-    return (int)plan->gsteps[(size_t)group].size();
+    if (!plan || group < 0 || group >= (int)plan->sch.gsteps.size()) { fail(STMMQR_ERR_INVALID, "no such front group"); return -1; }
+    return (int)plan->sch.gsteps[(size_t)group].size();
 }
 
 int stmmqr_factorize_step(stmmqr_plan *plan, int group, int step, int what, int cb_first, int cb_stride, int cb_count)
@@ -123,17 +123,17 @@ PanelMsg panel_msg(const FrontSym &s, long p)
 int stmmqr_plan_panel_doubles(stmmqr_plan *plan, stm_long f, stm_long *ndoubles)
 {
     if (!plan || f < 0 || f >= plan->nf || !ndoubles) return fail(STMMQR_ERR_INVALID, "bad front");
-    *ndoubles = (stm_long)panel_msg(plan->fs[f], 0).total;
+    *ndoubles = (stm_long)panel_msg(plan->sch.fs[f], 0).total;
     return 0;
 }
 
 static int panel_copy(stmmqr_plan &P, stm_long f, stm_long p, double *buf, int on_device, bool out, bool nosync = false)
 {
     if (f < 0 || f >= P.nf || !buf) return fail(STMMQR_ERR_INVALID, "bad front / buffer");
-    const FrontSym &s = P.fs[f];
+    const FrontSym &s = P.sch.fs[f];
     if (p < 0 || p >= s.npanels) return fail(STMMQR_ERR_INVALID, "no such panel");
     if (P.group[f] < 0) return fail(STMMQR_ERR_INVALID, "the front is not factorized by this plan");
-    if (!P.begun || !P.d_F.p || P.d_F.n != (size_t)P.farena)
+    if (!P.begun || !P.d_F.p || P.d_F.n != (size_t)P.sch.farena)
         return fail(STMMQR_ERR_INVALID, "panel messages move between factorize_begin and factorize_finish (the front arena of the current grouping must exist)");
     HIPCHK(hipSetDevice(P.device));
     const PanelMsg m = panel_msg(s, p);
@@ -142,7 +142,7 @@ static int panel_copy(stmmqr_plan &P, stm_long f, stm_long p, double *buf, int o
     if (on_device) {
         // device buffer: ONE launch packs / unpacks the six ranges
         void *homes[6] = {P.d_F.p + s.foff + (long long)p * STM_NB * s.ld,
-                          P.d_T.p + (long long)STM_TSLOT(P.h_tslot[(size_t)f], (int)p) * STM_NB * STM_NB, P.d_Tau.p + s.rp, P.d_Stair.p + s.rp,
+                          P.d_T.p + (long long)STM_TSLOT(P.sch.tslot[(size_t)f], (int)p) * STM_NB * STM_NB, P.d_Tau.p + s.rp, P.d_Stair.p + s.rp,
                           P.d_Rdead.p + s.col1, P.d_fnum.p + f};
         const long long offs[6] = {m.f_off * 8, m.t_off * 8, m.tau_off * 8, m.stair_off * 8, m.dead_off * 8, m.num_off * 8};
         const long long bytes[6] = {(long long)s.ld * m.nb * 8, 8LL * STM_NB * STM_NB, 8LL * s.fn, 4LL * s.fn, (long long)s.fp, (long long)sizeof(FrontNum)};
@@ -157,7 +157,7 @@ static int panel_copy(stmmqr_plan &P, stm_long f, stm_long p, double *buf, int o
         return 0;
     };
     LCHK(cp(P.d_F.p + s.foff + (long long)p * STM_NB * s.ld, m.f_off, (size_t)s.ld * (size_t)m.nb * sizeof(double)));
-    LCHK(cp(P.d_T.p + (long long)STM_TSLOT(P.h_tslot[(size_t)f], (int)p) * STM_NB * STM_NB, m.t_off, sizeof(double) * STM_NB * STM_NB));
+    LCHK(cp(P.d_T.p + (long long)STM_TSLOT(P.sch.tslot[(size_t)f], (int)p) * STM_NB * STM_NB, m.t_off, sizeof(double) * STM_NB * STM_NB));
     LCHK(cp(P.d_Tau.p + s.rp, m.tau_off, (size_t)s.fn * sizeof(double)));
     LCHK(cp(P.d_Stair.p + s.rp, m.stair_off, (size_t)s.fn * sizeof(int)));
     LCHK(cp(P.d_Rdead.p + s.col1, m.dead_off, (size_t)s.fp));
@@ -188,9 +188,9 @@ static int front_cols_copy(stmmqr_plan &P, stm_long f, int part, int nparts, dou
     HIPCHK(hipStreamSynchronize(P.stream));
     FrontNum nm;
     HIPCHK(hipMemcpy(&nm, P.d_fnum.p + f, sizeof nm, hipMemcpyDeviceToHost));
-    const FrontSym &s = P.fs[f];
+    const FrontSym &s = P.sch.fs[f];
     const long cn = s.fn - s.fp, cm = nm.cm;
-    if (cm < 0 || cm > cn || (long long)cm * (cm + 1) / 2 + (long long)cm * (cn - cm) > P.c_slot[(size_t)f])
+    if (cm < 0 || cm > cn || (long long)cm * (cm + 1) / 2 + (long long)cm * (cn - cm) > P.sch.c_slot[(size_t)f])
         return fail(STMMQR_ERR_INVALID, "front_cols: the front's contribution block does not fit its slot");
     auto coff = [&](long j) -> long long { return j < cm ? (long long)j * (j + 1) / 2 : (long long)cm * (cm + 1) / 2 + (long long)(j - cm) * cm; };
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : (out ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice);
@@ -251,7 +251,7 @@ SharedRing *ring_for(stmmqr_plan &P, stm_long f, int R)
         if (pr.first == &P && pr.second->f == f && pr.second->R == R) return pr.second;
     SharedRing *r = new SharedRing();
     r->f = f; r->R = R;
-    r->nd = panel_msg(P.fs[f], 0).total;
+    r->nd = panel_msg(P.sch.fs[f], 0).total;
     r->buf.assign((size_t)R, nullptr);
     r->ev_free.assign((size_t)R, nullptr);
     bool ok = true;
@@ -296,7 +296,7 @@ static int shared_front_loop(stmmqr_plan *plan, int group, stm_long f, int first
     if (P.device < 0 || P.device >= 64) return fail(STMMQR_ERR_INVALID, "device index out of range");
     if (!g_comm_stream[P.device]) HIPCHK(hipStreamCreateWithFlags(&g_comm_stream[P.device], hipStreamNonBlocking));
     hipStream_t cs = g_comm_stream[P.device], st = P.stream;
-    const int nsteps = (int)P.gsteps[(size_t)group].size();
+    const int nsteps = (int)P.sch.gsteps[(size_t)group].size();
     SharedRing *ring = ring_for(P, f, R);
     if (!ring) return fail(STMMQR_ERR_OUT_OF_MEMORY, "panel message buffers");
     const size_t bytes = (size_t)ring->nd * sizeof(double);
@@ -368,7 +368,7 @@ int stmmqr_factorize_shared_front(stmmqr_plan *plan, int group, stm_long f, int 
 // then trades blocks and row ids: two host synchronisations, two rounds of messages and a dozen interpreter calls per block.
 // Here a block is ONE message of a size the plan knows (its symbolic slot: stm_launch_front_msg), packed on the device, sent and
 // received on the plan's stream, unpacked on the device: nothing waits on the host. ----
-static long long front_msg_doubles(const stmmqr_plan &P, stm_long f) { return 8 + P.c_slot[(size_t)f] + (P.fs[f].fn - P.fs[f].fp); }
+static long long front_msg_doubles(const stmmqr_plan &P, stm_long f) { return 8 + P.sch.c_slot[(size_t)f] + (P.sch.fs[f].fn - P.sch.fs[f].fp); }
 
 static int msg_arena(stmmqr_plan &P, long long doubles)
 {
@@ -421,8 +421,8 @@ int stmmqr_factorize_exchange(stmmqr_plan *plan, stm_long nout, const stm_long *
             const int n = (int)std::min<size_t>(16, fr.size() - q0);
             for (int q = 0; q < n; q++) {
                 const stm_long f = fr[q0 + (size_t)q];
-                g.m[q].f = (int)f; g.m[q].off = off[q0 + (size_t)q]; g.m[q].slot = P.c_slot[(size_t)f];
-                mx = std::max(mx, P.c_slot[(size_t)f]);
+                g.m[q].f = (int)f; g.m[q].off = off[q0 + (size_t)q]; g.m[q].slot = P.sch.c_slot[(size_t)f];
+                mx = std::max(mx, P.sch.c_slot[(size_t)f]);
             }
             LCHK(stm_launch_front_msg(c, g, n, mx, P.d_msg.p, out, st));
             P.stats.nlaunch++;
@@ -449,7 +449,7 @@ int stmmqr_factorize_exchange(stmmqr_plan *plan, stm_long nout, const stm_long *
 // back (k_front_cols), sized by the symbolic bound of cm so that nobody asks the device for cm.
 static long long front_cols_bound(const stmmqr_plan &P, stm_long f, int part, int nparts, int *nown, long long *max_run)
 {
-    const FrontSym &s = P.fs[f];
+    const FrontSym &s = P.sch.fs[f];
     const long long cn = s.fn - s.fp, fm = s.fm_ub;
     const long long cm = P.do_rank ? std::min(fm, cn) : std::min(std::max(fm - std::min(fm, (long long)s.fp), 0LL), cn);
     auto coff = [&](long long j) -> long long { return j < cm ? j * (j + 1) / 2 : cm * (cm + 1) / 2 + (j - cm) * cm; };
@@ -475,7 +475,7 @@ int stmmqr_shared_front_gather(stmmqr_plan *plan, stm_long f, int first_rank, in
     if (f < 0 || f >= P.nf || (size_t)f >= P.shared.size() || !P.shared[(size_t)f]) return fail(STMMQR_ERR_INVALID, "not a shared front");
     const int R = nranks, i = tr->rank - first_rank;
     if (R < 1 || i < 0 || i >= R) return fail(STMMQR_ERR_INVALID, "this rank is not in the front's group");
-    if (R == 1 || P.fs[f].parent < 0) return 0;              // (the root's contribution block is empty)
+    if (R == 1 || P.sch.fs[f].parent < 0) return 0;              // (the root's contribution block is empty)
     HIPCHK(hipSetDevice(P.device));
     if (int e = stm_check_c_slot(P, f, 0, "stmmqr_shared_front_gather")) return e;
     std::vector<long long> nd((size_t)R, 0), mr((size_t)R, 0), off((size_t)R, 0);
@@ -542,7 +542,7 @@ int stmmqr_factorize_phases(stmmqr_plan *plan, const stmmqr_shard_phases *ph, co
             }
             need = std::max(need, t);
             const stm_long f = ph->shared_front[k];
-            if (f >= 0 && f < P.nf && ph->shared_span && ph->shared_first && P.fs[f].parent >= 0) {
+            if (f >= 0 && f < P.nf && ph->shared_span && ph->shared_first && P.sch.fs[f].parent >= 0) {
                 const int R = ph->shared_span[k], i = tr->rank - ph->shared_first[k];
                 long long g = 0, mr;
                 int no;
@@ -684,7 +684,7 @@ int stmmqr_plan_front_rhoff(stmmqr_plan *plan, stm_long f, stm_long *off)
     if (!plan || !plan->factored || f < 0 || f >= plan->nf || !off) return fail(STMMQR_ERR_INVALID, "bad front / no factorization held");
     stmmqr_plan &P = *plan;
     HIPCHK(hipSetDevice(P.device));
-    const FrontSym &s = P.fs[f];
+    const FrontSym &s = P.sch.fs[f];
     std::vector<long long> h((size_t)std::max(1, s.fn));
     if (s.fn > 0) HIPCHK(hipMemcpy(h.data(), P.d_Rhoff.p + s.rp, (size_t)s.fn * sizeof(long long), hipMemcpyDeviceToHost));
     for (int k = 0; k < s.fn; k++) off[k] = (stm_long)h[(size_t)k];
@@ -696,8 +696,8 @@ int stmmqr_plan_front_rhoff(stmmqr_plan *plan, stm_long f, stm_long *off)
    arena; -1 the plan does not recycle, or a bad f */
 int stmmqr_plan_front_kept(const stmmqr_plan *plan, stm_long f)
 {
-    if (!plan || !plan->recycle || f < 0 || f >= plan->nf || (size_t)f >= plan->kept.size()) return -1;
-    return plan->kept[(size_t)f] ? 1 : 0;
+    if (!plan || !plan->sch.recycle || f < 0 || f >= plan->nf || (size_t)f >= plan->sch.kept.size()) return -1;
+    return plan->sch.kept[(size_t)f] ? 1 : 0;
 }
 
 /* device memory held by the plan right now (bytes): arenas, factors, workspaces, index arrays */

@@ -1,10 +1,13 @@
 // stmmqr_plan.h -- the plan object and the helpers shared by the host translation units of libstmmqr_hip.so (local to the library):
 //   stmmqr_host.cpp      globals, options, device set-up and the side stream, device alloc / copy / free, shutdown
-//   stmmqr_planbuild.cpp the symbolic plan (build_plan), the pattern of A, plan create / destroy, stmmqr_plan_set_groups
+//   stmmqr_planbuild.cpp the symbolic plan (build_plan), the pattern of A, plan create / destroy, stmmqr_plan_set_groups; the ONE
+//                        place where a schedule goes into the plan and onto the device (stm_install_schedule), the arenas
 //   stmmqr_factorize.cpp the factorization driver: begin / group / finish / the whole call, around the pure recovery policy of
 //                        stmmqr_recover.h; its diagnostic prints in stmmqr_diag.cpp
 //   stmmqr_download.cpp  the factors out of the plan in the reference's layout (stmmqr_plan_download)
-//   stmmqr_schedule.cpp  arenas, the timeline allocator, the step timeline of every front group (stm_build_schedule)
+//   stmmqr_schedule.cpp  the pure planner (stmmqr_sched.h: no plan, no HIP call, no global): the symbolic sizes of the fronts, and
+//                        sched::build -- arena offsets, the timeline allocator, the step timeline of every front group -- which
+//                        returns the value stmmqr_plan::sch holds
 //   stmmqr_run.cpp       the step scheduler (stm_run_schedule: one step, serial, look-ahead, passengers), the pack pass
 //   stmmqr_multi.cpp     contribution blocks / panels in and out of a plan, shared fronts, the RCCL transport
 //   stmmqr_rfactor.cpp   Q-apply and triangular solves on the resident factors; with stmmqr_rcond.cpp (products with R,
@@ -35,6 +38,7 @@
 #include "stmmqr_internal.h"
 #include "stmmqr_knobs.h"
 #include "stmmqr_recover.h"
+#include "stmmqr_sched.h"              // (Step, sched::Schedule: the pure planner)
 
 
 extern thread_local std::string g_err;
@@ -99,33 +103,7 @@ template <class T> struct DevBuf {
 // column rj and the position rq of its value in A's storage) for A x.  Built on the host by stm_row_form (stmmqr_internal.h).
 struct AIndexDev { DevBuf<int> cp, ci, rp, rj, rq; };
 
-#include "stmmqr_resident.h"          // (Level, ResidentState: needs DevBuf)
-
-// One step of the factorization timeline.  Every front starts at the step after the last of its children has finished
-// (a small front takes one step, a big one a step per panel), so a front deep in a short branch does not wait for the
-// tallest front of its tree level: at every step the launches cover all the big fronts that are in flight, each at its
-// own panel.  Everything here is symbolic (lists built once per plan).
-struct Step {
-    int start_off = 0, n_start = 0, n_small = 0;      // fronts starting here (small first, then big): set up + assembled
-    int asm_parts_off = 0, asm_maxparts = 1, lds_small = 0;
-    int act_off = 0, plist_off = 0, n_act = 0;        // big fronts in flight + the panel each is at
-    int wp_off = 0;                                   // (index into d_wlists) their slices of the update workspace
-    int nsub = 1, nca = 1, nca_use = 0, npipe_use = 0, maxcb = 0, maxsl = 0, split = 0;
-    int lds_big = 0;       // dynamic LDS of the panel launch when every front may take the one-workgroup panel (recovery, tests)
-    int lds_plan = 0;      // ... when only the fronts planned for it do (the pipeline groups need the update's LDS only)
-    // the fronts in flight are listed in three classes: [0, n_norm) every panel's update on all trailing columns;
-    // then the sweep fronts (is_pair; w = 2 or 4 panels per sweep, stmmqr_plan::sweep) by panel number mod w: class r updates the
-    // column blocks 0 .. w-1-r only (the columns of the next panels), the last class then applies the w last panels at once to
-    // everything beyond
-    int n_norm = 0, n_pk[4] = {0, 0, 0, 0};
-    int maxsl_pk[4] = {0, 0, 0, 0}, maxcbp_po = 0;
-    int n_sweep() const { return n_pk[0] + n_pk[1] + n_pk[2] + n_pk[3]; }
-    int cpk_off = 0, cpk_parts_off = 0, n_cpk = 0, cpk_maxparts = 1;   // big fronts whose last panel runs here
-    // slab recycling: the fronts whose packed R+H block is staged at the end of this step (the small fronts that started here and
-    // the big fronts packed here, kept fronts excluded) + copy parts
-    int rhp_off = 0, rhp_parts_off = 0, n_rhp = 0, rhp_maxparts = 1;
-};
-
+#include "stmmqr_resident.h"          // (ResidentState: needs DevBuf)
 
 struct stmmqr_plan {
     int device = 0;
@@ -143,50 +121,22 @@ struct stmmqr_plan {
     int do_rank = 1;
     int keep_h = 1;                                    // QRsym->keepH: 0 = the packed blocks hold R only (qr_rhpack's keepH = 0 layout);
                                                        //  no Q-apply, one group only (stmmqr_plan_set_groups refuses)
-    int ca_min = STM_CA_MIN_ROWS;                      // (env STMMQR_CA_MIN when the schedule was built: experiments)
-    int plan_algo = 0;                                 // g_opt.panel_algo when the schedule was built
-    int tall_min = STM_TALL_MIN;                       // g_opt.tall_min_rows when the schedule was built
-    int tune = 0;                                      // env STMMQR_TUNE when the schedule was built (measurement sweeps)
     std::vector<long> Sp, Sj, Qfill, PLinv, Sleft, Child, Childp, Super, Rp, Rj, Post, Hip, Fm;
     bool has_qfill = false;
-    std::vector<FrontSym> fs;
-    std::vector<std::vector<Level>> glevels;   // [group][level]
-    std::vector<std::vector<Step>> gsteps;     // [group][step]
-    std::vector<long long> wlists;             // host copy of d_wlists
-    std::vector<char> pair_front;              // per front: takes the pair / quad update (plan time)
-    int sweep = 2;                             // panels per sweep of those fronts: 2 (k_upd_w2 / y2 / c2) or 4 (k_upd_wq / yq / cq)
+    // ---- what the planner reads (sched::Inputs): the grouping, the symbolic estimates, the recovery state
     std::vector<int> group;                    // per front: phase on this device, -1 = elsewhere
-    std::vector<int> h_tslot;                  // host copy of d_tslot
     std::vector<char> shared;                  // per front: STMMQR_GROUP_SHARED -- alone in its group, driven step by step
                                                //  (stmmqr_factorize_step), its trailing column blocks shared with other plans
-    std::vector<char> has_c;                   // per front: its packed contribution block has a slot in the C arena of this plan
-                                               //  (the front is factorized here, or it is a child of one that is: assign_arenas)
-    std::vector<long long> c_slot;             // ... and the size of that slot in doubles (the symbolic bound of csize)
-    int own_off = 0, n_own = 0;
-    // ---- slab recycling (the reference's stack discipline, SparseQR_factorize.c:405-422,925-933, re-cast for a timeline of steps):
-    // a front's slab lives from the step it starts to the step its contribution block is packed and its R+H block staged into the
-    // R+H arena; a contribution block from there to the step its parent starts.  Offsets are assigned by an address-ordered
-    // first-fit over that timeline (assign_arenas_timeline), all symbolic.  Fronts in `kept` keep their slab (never staged: their
-    // packed block is produced on the fly when the factors are downloaded) -- chosen where that makes the peak smaller (a root
-    // front that IS most of the factors).  Only plans that hold the whole tree in one group recycle (sharded plans: as before).
-    bool recycle = false;
     long maxstack = 0;                   // QRsym->maxstack (0: unknown)
-    std::vector<char> kept;              // per front
-    std::vector<int> f_t0, f_t1, c_t1;   // slab: [f_t0, f_t1]; contribution block: [f_t1, c_t1]  (steps of group 0)
-    long long rh_cap = 0;                // capacity of the R+H arena (doubles)
     long long rh_est_total = 0;          // all packed R+H blocks if no pivot column dies (symbolic; exact for full-rank input)
     std::vector<long long> rh_est_front; // ... per front (keepH = 0: the arena holds those of the fronts that do not keep their slab)
     double rh_est_scale = 1.0;           // ... times STMMQR_RH_EST_SCALE, read once when the plan is created (tests shrink the estimate)
-    bool early_end = false;              // the schedule of group 0 stops every front at the panel where it is expected to run out of rows
     recover::State rec;                  // what the planner reads of earlier failures (arena growth, full schedule), the last finish's outcome
-    std::vector<int> lists;              // host copy of d_lists
-    int post_off = 0, rh_parts_off = 0, rh_maxparts = 1;
-    long long farena = 0, carena = 0;
-    int tslots = 1;
-    int gp_slabs = 1;                    // Gram-based panel: max slab workgroups of a front
+    // ---- what the planner builds: the fronts (sch.fs) and everything a rebuild of the schedule replaces, as ONE value.  Written by
+    // stm_install_schedule alone (stmmqr_planbuild.cpp), which also bumps sched_gen; everyone else reads it
+    sched::Schedule sch;
+    long sched_gen = 0;                  // schedule generation: what the resident tables and a captured graph were built from
     long long tpanels = 0;               // panels of all fronts: one kept T each (Q-apply on the resident factors)
-    long long wp_doubles = 0;            // workspace of the row-parallel update (partial W blocks)
-    long long wp2_doubles = 0;           // ... of the side stream's copy: steps with pair-update fronts never go there
     bool pattern_set = false;
     double bytes_assemble_idx = 0;       // index bytes of the assembly (symbolic part of SURVEY 8d formula)
 
@@ -199,8 +149,6 @@ struct stmmqr_plan {
     DevBuf<long long> d_wlists;
     DevBuf<double> d_Ypend;                    // -Y of the pair-update fronts, by absolute column block (DevCtx::Ypend)
     DevBuf<long long> d_ypoff;                 // [nf] offsets into it (-1: not a pair-update front)
-    std::vector<long long> ypoff;
-    long long yp_doubles = 0;
     DevBuf<double> d_msg;                // subtree exchange: message buffers (stmmqr_factorize_exchange, grown on demand)
     DevBuf<int> d_wcnt, d_wcnt2;         // per column block of the update workspaces: slab tickets (zero between launches)
     DevBuf<int> d_wflag, d_wflag2;       // ... fused update: step + 1 once W2 of the column block is in its slot
@@ -225,9 +173,17 @@ struct stmmqr_plan {
     long rank = 0;
     std::vector<FrontNum> h_fnum;
     ResidentState res;                   // everything the operations on the resident factors keep (stmmqr_resident.h)
-    hipGraphExec_t graph_exec = nullptr;           // options.use_graph: the captured schedule of group 0
-    double graph_tol = 0; int graph_ntol = 0, graph_dbg = 0; unsigned long long graph_opt = 0; long graph_nlaunch = 0;
-    long sched_gen = 0, graph_gen = -1;            // schedule generation (bumped by every stm_build_schedule) / the captured one
+    // options.use_graph: the captured schedule of group 0, and what it was captured under -- everything that travels in the kernel
+    // arguments or decides what is launched (ensure_graph compares keys; stm_install_schedule clears the capture)
+    struct Graph {
+        struct Key {
+            double tol = 0; int ntol = 0, dbg = 0; unsigned long long opt = 0; long gen = -1;
+            bool operator==(const Key &o) const { return tol == o.tol && ntol == o.ntol && dbg == o.dbg && opt == o.opt && gen == o.gen; }
+        } key;
+        hipGraphExec_t exec = nullptr;
+        long nlaunch = 0;                          // launches of one replay (host statistics)
+        void clear() { if (exec) (void)hipGraphExecDestroy(exec); exec = nullptr; nlaunch = 0; }
+    } graph;
     double last_tol = 0;
     long last_ntol = 0;
     stmmqr_stats stats = {};
@@ -255,18 +211,18 @@ struct stmmqr_plan {
         DevCtx c;
         c.fs = d_fs.p; c.fnum = d_fnum.p; c.Farena = d_F.p; c.Carena = d_C.p; c.Tws = d_T.p; c.tslot = d_tslot.p;
         c.Tall = d_Tall.p;
-        c.Gp = d_Gp.p; c.gp_slabs = gp_slabs; c.sig = d_sig.p; c.panel_algo = serial_panels ? 1 : plan_algo; c.ca_min_rows = ca_min;
+        c.Gp = d_Gp.p; c.gp_slabs = sch.gp_slabs; c.sig = d_sig.p; c.panel_algo = serial_panels ? 1 : sch.plan_algo; c.ca_min_rows = sch.ca_min;
         c.Sx = d_Sx.p; c.Sp = d_Sp.p; c.Sjrel = d_Sjrel.p; c.Sj0 = d_Sj0.p; c.Sleft = d_Sleft.p;
         c.Child = d_Child.p; c.Rjrel = d_Rjrel.p; c.Stair = d_Stair.p; c.Tau = d_Tau.p; c.Hii = d_Hii.p;
         c.Rdead = d_Rdead.p; c.Cmap = d_Cmap.p; c.Cursor = d_Cursor.p; c.Rhoff = d_Rhoff.p; c.Rboff = d_Rboff.p;
         c.tol = last_tol; c.ntol = (int)last_ntol;
         c.dbg = dbg;
-        c.sweep = sweep;
-        c.tune = tune;                                            // (env STMMQR_TUNE when the schedule was built)
+        c.sweep = sch.sweep;
+        c.tune = sch.tune;                                            // (env STMMQR_TUNE when the schedule was built)
         c.Ypend = d_Ypend.p; c.ypoff = d_ypoff.p;
-        c.rh_top = recycle ? d_rhtop.p : nullptr; c.rh_cap = rh_cap;
+        c.rh_top = sch.recycle ? d_rhtop.p : nullptr; c.rh_cap = sch.rh_cap;
         if (serial_panels) c.dbg = (c.dbg & ~(2048 | 4096)) | 256;   // the one-workgroup LDS / in-place panel for every panel
-        c.tall_min = tall_min;
+        c.tall_min = sch.tall_min;
         c.cbskip = 0;
         c.dbgbuf = d_dbg.p;
         c.abort = d_abort.p;
@@ -277,7 +233,7 @@ struct stmmqr_plan {
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto &q : evpairs) { if (q.a) (void)hipEventDestroy(q.a); if (q.b) (void)hipEventDestroy(q.b); }
-        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+        graph.clear();
         for (auto *v : {&ev_main, &ev_prep, &ev_side})
             for (auto &e : *v)
                 if (e) (void)hipEventDestroy(e);
@@ -288,11 +244,8 @@ struct stmmqr_plan {
 // One piece of one timeline step (stmmqr_factorize_step): what = STMMQR_STEP_* bits; the update takes the column blocks
 // cb_first, cb_first + cb_stride, ... (at most cb_count of them when cb_count >= 0) of the step's fronts.
 struct StepReq { int step, what, cb_first, cb_stride, cb_count; };
-// planner (stmmqr_schedule.cpp) and scheduler (stmmqr_run.cpp) entry points used by the other host translation units
-void stm_assign_arenas(stmmqr_plan &P);
-int stm_ensure_arenas(stmmqr_plan &P);
-void stm_build_schedule(stmmqr_plan &P, std::vector<int> &tslot);
-int stm_upload_recycle(stmmqr_plan &P);
+// scheduler (stmmqr_run.cpp) and plan (stmmqr_planbuild.cpp) entry points used by the other host translation units
+int stm_ensure_arenas(stmmqr_plan &P);                                 // (stmmqr_planbuild.cpp)
 int stm_run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req);
 int stm_run_pack(stmmqr_plan &P, bool &overflow);
 int stm_ensure_la_events(stmmqr_plan &P, size_t nsteps, const knobs::RunKnobs &k);

@@ -1,12 +1,67 @@
-// stmmqr_planbuild.cpp -- everything of a plan that depends only on the symbolic analysis and the pattern of A: build_plan (sizes,
-// relative indices, the estimate of the packed factors, the first schedule and the plan's device memory), the S -> A map of a
-// pattern, plan create / destroy, the regrouping of the fronts (stmmqr_plan_set_groups) and the index of A for the products with A.
+// stmmqr_planbuild.cpp -- the plan around the pure planner (stmmqr_sched.h): build_plan (the symbolic arrays, relative indices and the
+// plan's device memory), the S -> A map of a pattern, plan create / destroy, the regrouping of the fronts (stmmqr_plan_set_groups),
+// the index of A for the products with A -- and stm_install_schedule, the one place where a schedule goes into a plan and onto the device.
 //
 // Reference counterparts (paths relative to /root/reference/STMMQR):
 //   stmmqr_plan_create      the allocation / setup half of qr_factorize   src/qr/SparseQR_factorize.c:222-498
 #include "stmmqr_plan.h"
 
 namespace {
+
+// The schedule of the plan's grouping (P.group / P.shared) over the fronts `fs`: the plan's symbolic data, the options, knobs and
+// recovery state as they are NOW, handed to the pure builder.
+sched::Schedule plan_schedule(const stmmqr_plan &P, const std::vector<FrontSym> &fs)
+{
+    const sched::Inputs in{P.nf, P.Post, P.Child, P.Childp, fs, P.do_rank, P.keep_h, P.maxstack, P.rh_est_total, P.rh_est_front, P.rh_est_scale,
+                           P.group, P.shared, {g_opt.big_front_cols, g_opt.pair_update, g_opt.tall_min_rows, g_opt.panel_algo},
+                           knobs::BuildKnobs::read(), knobs::once<knobs::K_PART_GRAIN>(), knobs::once<knobs::K_PART_CAP>(),
+                           P.rec.overflowed, P.rec.rh_grow, P.rec.full_schedule, P.rec.early_phased};
+    return sched::build(in);
+}
+
+// The ONE place where a schedule goes into the plan and onto the device (a fresh plan, a regrouping, a rebuild of the recovery): a
+// captured graph describes the old step lists and workspaces and goes; the fronts, the recycling's device side, the lists; the
+// workspaces and tickets only grow (a regrouping of the same tree usually needs what it needed before; on a fresh plan that is
+// "allocate").  The front arenas follow at the next stmmqr_factorize_begin (stm_ensure_arenas).
+int stm_install_schedule(stmmqr_plan &P, sched::Schedule &&S)
+{
+    hipStream_t st = P.stream;
+    P.graph.clear();
+    P.sch = std::move(S);
+    P.sched_gen++;
+    const sched::Schedule &Z = P.sch;
+    LCHK(P.d_fs.upload(Z.fs, st));
+    // slab recycling: bump words, Post-order offsets, kept flags; the R+H arena and the resident scratch of the old schedule go
+    if (!P.d_rhtop.p) LCHK(P.d_rhtop.alloc(2));
+    if (!P.d_fin.p || P.d_fin.n < (size_t)std::max(1L, P.nf)) LCHK(P.d_fin.alloc((size_t)std::max(1L, P.nf)));
+    HIPCHK(hipMemsetAsync(P.d_rhtop.p, 0, 2 * sizeof(long long), st));
+    if (Z.recycle) {
+        LCHK(P.d_kept.upload(Z.kept, st));
+        HIPCHK(hipStreamSynchronize(st));
+        P.res.sched.d_scr.release();                             // (allocated by the first resident-factor operation: ensure_scratch)
+        P.d_RH.release();                                        // (the arena follows with the front arenas: stm_ensure_arenas)
+    }
+    auto grow = [](auto &buf, size_t n) -> int { return buf.n >= n && buf.p ? 0 : buf.alloc(n); };
+    LCHK(grow(P.d_T, (size_t)STM_PD_RING * Z.tslots * STM_NB * STM_NB));
+    LCHK(grow(P.d_Gp, (size_t)Z.tslots * (Z.gp_slabs + 1) * STM_NB * STM_NB));
+    LCHK(grow(P.d_Wp, (size_t)Z.wp_doubles));
+    LCHK(grow(P.d_Ypend, (size_t)std::max(1LL, Z.yp_doubles)));
+    LCHK(P.d_ypoff.upload(Z.ypoff, st));
+    LCHK(grow(P.d_Wp2, (size_t)std::max(1LL, Z.wp2_doubles)));
+    P.wcnt_n = std::max(P.wcnt_n, (size_t)(Z.wp_doubles / (STM_NB * 32) + 1));
+    LCHK(grow(P.d_wcnt, P.wcnt_n));
+    LCHK(grow(P.d_wcnt2, P.wcnt_n));
+    LCHK(grow(P.d_wflag, P.wcnt_n));
+    if (!P.d_abort.p) LCHK(P.d_abort.alloc(4));
+    LCHK(grow(P.d_wflag2, P.wcnt_n));
+    HIPCHK(hipMemset(P.d_wcnt.p, 0, P.wcnt_n * sizeof(int)));
+    HIPCHK(hipMemset(P.d_wcnt2.p, 0, P.wcnt_n * sizeof(int)));
+    LCHK(P.d_tslot.upload(Z.tslot, st));
+    LCHK(P.d_lists.upload(Z.lists, st));
+    LCHK(P.d_wlists.upload(Z.wlists, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // planner: everything that depends only on the symbolic analysis
@@ -33,79 +88,13 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
     P.has_qfill = v.Qfill != nullptr;
     if (P.has_qfill) cp(P.Qfill, v.Qfill, n);
 
-    // ---- per-front symbolic sizes -----------------------------------------------------------
-    std::vector<long> parent(nf, -1);
-    for (long f = 0; f < nf; f++)
-        for (long q = P.Childp[f]; q < P.Childp[f + 1]; q++) parent[P.Child[q]] = f;
-
-    // upper bound on the rows of every front: taken from the analysis when given (QRsym->Fm, worst case when
-    // rank detection is on: SparseQR_analyze.c:461-471), otherwise recomputed with the same recurrence
-    P.Fm.assign(nf, 0);
-    if (v.Fm) {
-        for (long f = 0; f < nf; f++) P.Fm[f] = v.Fm[f];
-    } else {
-        std::vector<long> cmub(nf, 0);
-        for (long kf = 0; kf < nf; kf++) {
-            const long f = P.Post[kf];
-            const long fp = P.Super[f + 1] - P.Super[f], fn = P.Rp[f + 1] - P.Rp[f];
-            long fm = P.Sleft[P.Super[f + 1]] - P.Sleft[P.Super[f]];
-            for (long q = P.Childp[f]; q < P.Childp[f + 1]; q++) fm += cmub[P.Child[q]];
-            P.Fm[f] = fm;
-            const long cn = fn - fp;
-            cmub[f] = P.do_rank ? std::min(fm, cn) : std::min(std::max(fm - std::min(fm, fp), 0L), cn);
-        }
-    }
-
-    // the row count every front will have if no pivot column dies (exact for full-rank input): used only to plan the
-    // number of panel launches (stm_tall_panel); the kernels cope with any actual row count
-    std::vector<long> fmest(nf, 0), cmest(nf, 0);
-    for (long kf = 0; kf < nf; kf++) {
-        const long f = P.Post[kf];
-        const long fp = P.Super[f + 1] - P.Super[f], fn = P.Rp[f + 1] - P.Rp[f];
-        long fe = P.Sleft[P.Super[f + 1]] - P.Sleft[P.Super[f]];
-        for (long q = P.Childp[f]; q < P.Childp[f + 1]; q++) fe += cmest[P.Child[q]];
-        fmest[f] = std::min(fe, P.Fm[f]);
-        cmest[f] = std::min(std::max(fe - std::min(fe, fp), 0L), fn - fp);
-    }
-
-    P.fs.assign(nf, FrontSym());
-    long long foff = 0, coff = 0, tpan_total = 0;
-    for (long kf = 0; kf < nf; kf++) {
-        const long f = P.Post[kf];
-        FrontSym &s = P.fs[f];
-        const long fp = P.Super[f + 1] - P.Super[f], fn = P.Rp[f + 1] - P.Rp[f];
-        const long fm = P.Fm[f];
-        // (front-local offsets are 64-bit on the device: row + column * ld; rows and columns themselves are int32)
-        if (fm * fn >= (1L << 36)) return fail(STMMQR_ERR_TOO_LARGE, "a single front exceeds 2^36 entries");
-        s.fn = (int)fn; s.fp = (int)fp; s.col1 = (int)P.Super[f]; s.rp = (int)P.Rp[f]; s.hip = (int)P.Hip[f];
-        s.child0 = (int)P.Childp[f]; s.child1 = (int)P.Childp[f + 1];
-        s.srow0 = (int)P.Sleft[P.Super[f]]; s.srow1 = (int)P.Sleft[P.Super[f + 1]];
-        s.fm_ub = (int)fm;
-        s.fm_est = (int)fmest[f];
-        s.ld = (int)std::max(2L, (fm + 1) & ~1L);
-        s.npanels = (int)((fn + STM_NB - 1) / STM_NB);
-        s.tpan = (int)tpan_total;
-        tpan_total += s.npanels;
-        {
-            // Q-apply: fronts with this many entries or more are split over workgroups (k_qbig_*); STMMQR_QBIG_MIN
-            // overrides the threshold (tests send small fronts through that path).  2 M entries until round 4; with the grouped launches
-            // (k_qbig_step4) smaller fronts pay too, at 256 KB of T4 per four panels -- default workload, threshold: Q'b / solve ms,
-            // GB of T4: 2 M 13.1 / 20.6, 0.31; 1 M 12.5 / 20.0, 0.39; 256 K 11.9 / 19.5, 0.61; 128 K 11.6 / 19.2, 0.81.  1 M.
-            const long qbig_min = knobs::num(knobs::K_QBIG_MIN);
-            // ... and, whatever its entry count, a front that one workgroup cannot hold in LDS: a tall thin one (16 363 rows at 40
-            // columns) or a short wide one whose columns are all pivotal (10 921 of them) -- the split kernels have no such limit
-            const bool over_lds = stm_lds_qapply(fm, fn) > STM_RES_LDS_MAX || stm_lds_rsolve(fp, fn) > STM_RES_LDS_MAX;
-            s.qbig = ((fm * fn >= qbig_min || over_lds) && fn >= 1) ? 1 : 0;
-            // R' x = b: the one-workgroup kernel keeps the front's u and x in LDS (6 550 columns of a square-ish front, 10 890 of a
-            // short wide one); a front beyond that is split over its columns (k_rtbig_*) by the pass that knows how, rt_pass in mode RT_SPLIT.
-            // STMMQR_RTBIG_MIN splits smaller ones too
-            s.rtbig = (stm_lds_rtsolve(fp, fm, fn) > STM_RES_LDS_MAX || fm * fn >= knobs::num(knobs::K_RTBIG_MIN)) ? 1 : 0;
-        }
-        s.parent = (int)parent[f];
-        s.foff = 0; s.coff = 0;                                    // (stm_assign_arenas, once the groups are known)
-    }
-    (void)foff; (void)coff;
-    P.tpanels = tpan_total;
+    // ---- per-front symbolic sizes (pure: stmmqr_schedule.cpp) ----
+    const sched::Symbolic sv{nf, P.Sleft, P.Super, P.Rp, P.Hip, P.Child, P.Childp, P.Post, v.Fm, P.do_rank, P.keep_h,
+                             knobs::num(knobs::K_QBIG_MIN), knobs::num(knobs::K_RTBIG_MIN)};
+    sched::Fronts F;
+    std::string why;
+    if (sched::front_syms(sv, F, why)) return fail(STMMQR_ERR_TOO_LARGE, why);
+    P.tpanels = F.tpanels;
 
     // ---- relative indices (value independent): child column -> parent column, S entry -> front column ----
     std::vector<int> Rjrel(std::max(1L, v.rjsize), 0), Sjrel(std::max(1L, v.anz), 0), Sj0(std::max(1L, m), -1);
@@ -114,7 +103,7 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
         for (long f = 0; f < nf; f++) {
             const long p1 = P.Rp[f], fn = P.Rp[f + 1] - p1;
             for (long j = 0; j < fn; j++) Fmap[P.Rj[p1 + j]] = (int)j;
-            for (long r = P.fs[f].srow0; r < P.fs[f].srow1; r++)
+            for (long r = F.fs[f].srow0; r < F.fs[f].srow1; r++)
                 for (long p = P.Sp[r]; p < P.Sp[r + 1]; p++) Sjrel[p] = Fmap[P.Sj[p]];
             for (long q = P.Childp[f]; q < P.Childp[f + 1]; q++) {
                 const long c = P.Child[q];
@@ -127,46 +116,14 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
             if (P.Sp[r + 1] > P.Sp[r]) Sj0[r] = (int)P.Sj[P.Sp[r]];
         P.bytes_assemble_idx += 4.0 * (double)v.anz;
     }
-    // ---- size of every packed R+H block if no pivot column dies (exact for full-rank input): the symbolic staircase of the front
-    // (qr_fsize: rows of S by leftmost column + the children's contribution rows, whose leftmost columns are the columns of their
-    // C) run through qr_front's row bookkeeping (:1434-1609) and qr_rhpack's column lengths (:1691-1784).  Sizes the R+H arena of
-    // the slab recycling (with a margin; QRsym->maxstack is the hard bound the arena falls back to) ----
-    P.rh_est_total = 0;
-    P.rh_est_front.assign((size_t)std::max(1L, nf), 0);
-    {
-        std::vector<long> stair;
-        for (long kf = 0; kf < nf; kf++) {
-            const long f = P.Post[kf];
-            const long fp = P.fs[f].fp, fn = P.fs[f].fn, fm = fmest[f];
-            stair.assign((size_t)fn + 1, 0);
-            for (long j = 0; j < fp; j++) stair[(size_t)j] = P.Sleft[P.Super[f] + j + 1] - P.Sleft[P.Super[f] + j];
-            for (long q = P.Childp[f]; q < P.Childp[f + 1]; q++) {
-                const long c = P.Child[q];
-                const long fpc = P.Super[c + 1] - P.Super[c], pc = P.Rp[c] + fpc;
-                for (long i = 0; i < cmest[c]; i++) stair[(size_t)Rjrel[(size_t)(pc + i)]]++;
-            }
-            long run = 0;
-            for (long j = 0; j < fn; j++) { run += stair[(size_t)j]; stair[(size_t)j] = run; }       // rows with leftmost column <= j
-            long g = 0, rm = 0;
-            long long sz = 0;
-            for (long k = 0; k < fn; k++) {
-                long t;
-                if (g >= fm) t = (k < fp) ? 0 : fm;                       // rows ran out
-                else { t = std::min(fm, std::max(g + 1, stair[(size_t)k])); g++; }
-                if (!P.keep_h) { if (k < fp && t > 0 && rm < fm) rm++; sz += rm; continue; }   // (R only: rm rows per column)
-                if (k < fp) { if (t > 0) rm++; sz += (t > 0) ? t : rm; }
-                else { const long h = std::min(rm + (k - fp) + 1, fm); sz += rm + std::max(t - h, 0L); }
-            }
-            P.rh_est_total += sz;
-            P.rh_est_front[(size_t)f] = sz;
-        }
-    }
+    sched::rh_estimate(sv, Rjrel, F);                            // (sizes the R+H arena of the slab recycling)
+    P.Fm.swap(F.Fm);
+    P.rh_est_total = F.rh_est_total;
+    P.rh_est_front.swap(F.rh_est_front);
 
     // ---- level schedule: one group holding every front (multi-GPU callers regroup with set_groups) ----
     P.group.assign(nf, 0);
-    stm_assign_arenas(P);
-    std::vector<int> tslot;
-    stm_build_schedule(P, tslot);
+    sched::Schedule S = plan_schedule(P, F.fs);
 
     // ---- device memory ----------------------------------------------------------------------------
     size_t freeb = 0, totalb = 0;
@@ -181,25 +138,10 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
         std::vector<int> t(h.begin(), h.end());
         return d.upload(t, st);
     };
-    LCHK(P.d_fs.upload(P.fs, st));
+    LCHK(stm_install_schedule(P, std::move(S)));
     LCHK(P.d_fnum.alloc(std::max(1L, nf)));
     HIPCHK(hipMemsetAsync(P.d_fnum.p, 0, std::max(1L, nf) * sizeof(FrontNum), st));
-    LCHK(P.d_T.alloc((size_t)STM_PD_RING * P.tslots * STM_NB * STM_NB));
-    LCHK(P.d_Gp.alloc((size_t)P.tslots * (P.gp_slabs + 1) * STM_NB * STM_NB));
     LCHK(P.d_Tall.alloc((size_t)std::max(1LL, P.tpanels) * STM_NB * STM_NB));
-    LCHK(P.d_Wp.alloc((size_t)P.wp_doubles));
-    LCHK(P.d_Ypend.alloc((size_t)std::max(1LL, P.yp_doubles)));
-    LCHK(P.d_ypoff.upload(P.ypoff, st));
-    LCHK(P.d_Wp2.alloc((size_t)std::max(1LL, P.wp2_doubles)));
-    P.wcnt_n = (size_t)(P.wp_doubles / (STM_NB * 32) + 1);
-    LCHK(P.d_wcnt.alloc(P.wcnt_n));
-    LCHK(P.d_wcnt2.alloc(P.wcnt_n));
-    LCHK(P.d_wflag.alloc(P.wcnt_n));
-    if (!P.d_abort.p) LCHK(P.d_abort.alloc(4));
-    LCHK(P.d_wflag2.alloc(P.wcnt_n));
-    HIPCHK(hipMemset(P.d_wcnt.p, 0, P.wcnt_n * sizeof(int)));
-    HIPCHK(hipMemset(P.d_wcnt2.p, 0, P.wcnt_n * sizeof(int)));
-    LCHK(P.d_tslot.upload(tslot, st));
     LCHK(P.d_Sx.alloc((size_t)v.anz));
     LCHK(P.d_Ax.alloc((size_t)v.anz));
     LCHK(P.d_smap.alloc((size_t)v.anz));
@@ -222,14 +164,32 @@ int build_plan(stmmqr_plan &P, const stmmqr_symbolic_view &v)
     LCHK(P.d_sig.alloc(2));
     HIPCHK(hipMemsetAsync(P.d_dbg.p, 0, 2048 * sizeof(unsigned long long), st));
     LCHK(P.d_Rdead.alloc((size_t)std::max(1L, n)));
-    LCHK(P.d_lists.upload(P.lists, st));
-    LCHK(P.d_wlists.upload(P.wlists, st));
     HIPCHK(hipStreamSynchronize(st));
-    LCHK(stm_upload_recycle(P));
     return 0;
 }
 
 }  // namespace
+
+// the arenas themselves: (re)allocated when their size changed (first factorization of a plan, or after a regrouping)
+int stm_ensure_arenas(stmmqr_plan &P)
+{
+    const sched::Schedule &Z = P.sch;
+    if (P.d_F.p && P.d_F.n == (size_t)Z.farena && P.d_C.p && P.d_C.n == (size_t)Z.carena &&
+        (!Z.recycle || (P.d_RH.p && P.d_RH.n == (size_t)Z.rh_cap)))
+        return 0;
+    HIPCHK(hipStreamSynchronize(P.stream));
+    if (P.d_F.n != (size_t)Z.farena) P.d_F.release();
+    if (P.d_C.n != (size_t)Z.carena) P.d_C.release();
+    size_t freeb = 0, totalb = 0;
+    HIPCHK(hipMemGetInfo(&freeb, &totalb));
+    const double need = 8.0 * ((P.d_F.p ? 0.0 : (double)Z.farena) + (P.d_C.p ? 0.0 : (double)Z.carena) +
+                               ((Z.recycle && P.d_RH.n != (size_t)Z.rh_cap) ? (double)Z.rh_cap : 0.0)) * 1.02;
+    if (need > 0.95 * (double)freeb) return fail(STMMQR_ERR_OUT_OF_MEMORY, "front arena does not fit in free HBM");
+    if (!P.d_F.p) LCHK(P.d_F.alloc((size_t)Z.farena));
+    if (!P.d_C.p) LCHK(P.d_C.alloc((size_t)Z.carena));
+    if (Z.recycle && P.d_RH.n != (size_t)Z.rh_cap) LCHK(P.d_RH.alloc((size_t)Z.rh_cap));
+    return 0;
+}
 
 // qr_stranspose2 as a symbolic map: smap[s] = p such that Sx[s] = Ax[p]  (SparseQR_factorize.c:755-785)
 int stm_set_pattern(stmmqr_plan &P, const stm_long *Ap, const stm_long *Ai)
@@ -355,7 +315,7 @@ int stmmqr_plan_set_groups(stmmqr_plan *plan, const int *group)
             cnt[(size_t)g]++;
             if (group[f] & STMMQR_GROUP_SHARED) {
                 nsh[(size_t)g]++;
-                if (!(P.fs[f].fn >= g_opt.big_front_cols && P.fs[f].fm_ub >= 64))
+                if (!sched::is_big(P.sch.fs[f], g_opt.big_front_cols))
                     return fail(STMMQR_ERR_INVALID, "a shared front must be one of the large fronts (options.big_front_cols)");
             }
         }
@@ -369,36 +329,9 @@ int stmmqr_plan_set_groups(stmmqr_plan *plan, const int *group)
         P.group[f] = gid(f);
         P.shared[(size_t)f] = (group[f] >= 0 && (group[f] & STMMQR_GROUP_SHARED)) ? 1 : 0;
     }
-    // a captured schedule describes the old step lists and workspaces
-    if (P.graph_exec) { (void)hipGraphExecDestroy(P.graph_exec); P.graph_exec = nullptr; }
-    P.graph_nlaunch = 0;
-    stm_assign_arenas(P);                                        // (the arenas follow at the next stmmqr_factorize_begin)
     P.factored = false;                                      // (the factors of the old grouping live at the old offsets)
-    std::vector<int> tslot;
-    stm_build_schedule(P, tslot);                                // (a plan that holds the whole tree again recycles its slabs: new offsets)
-    LCHK(P.d_fs.upload(P.fs, P.stream));
-    LCHK(stm_upload_recycle(P));
-    // workspaces only grow (a regrouping of the same tree usually needs what it needed before)
-    auto grow = [](auto &buf, size_t n) -> int { return buf.n >= n && buf.p ? 0 : buf.alloc(n); };
-    LCHK(grow(P.d_T, (size_t)STM_PD_RING * P.tslots * STM_NB * STM_NB));
-    LCHK(grow(P.d_Gp, (size_t)P.tslots * (P.gp_slabs + 1) * STM_NB * STM_NB));
-    LCHK(grow(P.d_Wp, (size_t)P.wp_doubles));
-    LCHK(grow(P.d_Ypend, (size_t)std::max(1LL, P.yp_doubles)));
-    LCHK(P.d_ypoff.upload(P.ypoff, P.stream));
-    LCHK(grow(P.d_Wp2, (size_t)std::max(1LL, P.wp2_doubles)));
-    P.wcnt_n = std::max(P.wcnt_n, (size_t)(P.wp_doubles / (STM_NB * 32) + 1));
-    LCHK(grow(P.d_wcnt, P.wcnt_n));
-    LCHK(grow(P.d_wcnt2, P.wcnt_n));
-    LCHK(grow(P.d_wflag, P.wcnt_n));
-    if (!P.d_abort.p) LCHK(P.d_abort.alloc(4));
-    LCHK(grow(P.d_wflag2, P.wcnt_n));
-    HIPCHK(hipMemset(P.d_wcnt.p, 0, P.wcnt_n * sizeof(int)));
-    HIPCHK(hipMemset(P.d_wcnt2.p, 0, P.wcnt_n * sizeof(int)));
-    LCHK(P.d_tslot.upload(tslot, P.stream));
-    LCHK(P.d_lists.upload(P.lists, P.stream));
-    LCHK(P.d_wlists.upload(P.wlists, P.stream));
-    HIPCHK(hipStreamSynchronize(P.stream));
-    return 0;
+    // (a plan that holds the whole tree again recycles its slabs: new offsets; the arenas follow at the next stmmqr_factorize_begin)
+    return stm_install_schedule(P, plan_schedule(P, P.sch.fs));
 }
 
 // Does front f have a contribution-block slot on this plan, allocated, that holds `csize` doubles?  A front that is neither
@@ -407,16 +340,16 @@ int stmmqr_plan_set_groups(stmmqr_plan *plan, const int *group)
 int stm_check_c_slot(const stmmqr_plan &P, stm_long f, long long csize, const char *what)
 {
     if (f < 0 || f >= P.nf) return fail(STMMQR_ERR_INVALID, std::string(what) + ": no such front");
-    if (P.recycle)
+    if (P.sch.recycle)
         return fail(STMMQR_ERR_INVALID, std::string(what) + ": this plan holds the whole tree and recycles its contribution blocks "
                                         "(nothing to exchange; regroup with stmmqr_plan_set_groups first)");
-    if ((size_t)f >= P.has_c.size() || !P.has_c[(size_t)f])
+    if ((size_t)f >= P.sch.has_c.size() || !P.sch.has_c[(size_t)f])
         return fail(STMMQR_ERR_INVALID, std::string(what) + ": the front has no contribution-block slot on this plan (it is neither "
                                         "factorized here nor a child of a front that is)");
-    if (!P.d_C.p || P.d_C.n != (size_t)P.carena)
+    if (!P.d_C.p || P.d_C.n != (size_t)P.sch.carena)
         return fail(STMMQR_ERR_INVALID, std::string(what) + ": the arenas of the current grouping are not allocated yet "
                                         "(stmmqr_factorize_begin comes first)");
-    if (csize < 0 || csize > P.c_slot[(size_t)f])
+    if (csize < 0 || csize > P.sch.c_slot[(size_t)f])
         return fail(STMMQR_ERR_INVALID, std::string(what) + ": the block exceeds the front's slot");
     return 0;
 }

@@ -37,10 +37,10 @@ int selected_inverse(stmmqr_plan *plan, stm_long ncol, double *var, int on_devic
     PASS(begin_resident_op(P));
     if (ncol == 0) return 0;
     hipStream_t st = P.stream;
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     const long nf = P.nf;
     // ---- the view and where every front's block lies ----
-    const restab::SelInvLayout &Y = si.lay = restab::selinv_layout(P.fs, LV, P.lists, P.Rj, ncol);
+    const restab::SelInvLayout &Y = si.lay = restab::selinv_layout(P.sch.fs, LV, P.sch.lists, P.Rj, ncol);
     // ---- the call's own device memory ----
     const bool own_var = !on_device || !var;
     const size_t rjs = (size_t)std::max(1L, P.rjsize);
@@ -138,7 +138,7 @@ int stmmqr_plan_covariance_entries(stmmqr_plan *plan, stm_long ncol, stm_long np
     SelInv si;
     PASS(selected_inverse(plan, ncol, nullptr, 0, [&](stmmqr_plan &P) {
         std::string msg;
-        return restab::resolve_pairs(P.fs, P.Super, P.Rj, P.has_qfill ? P.Qfill.data() : nullptr, ncol, npairs, I, J, trip, msg)
+        return restab::resolve_pairs(P.sch.fs, P.Super, P.Rj, P.has_qfill ? P.Qfill.data() : nullptr, ncol, npairs, I, J, trip, msg)
                    ? fail(STMMQR_ERR_INVALID, msg) : 0;
     }, si));
     if (npairs == 0 || !si.ran) return si.ran ? end_resident_op(*plan) : 0;

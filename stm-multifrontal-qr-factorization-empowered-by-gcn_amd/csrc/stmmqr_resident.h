@@ -12,9 +12,9 @@
 #include "stmmqr_restables.h"
 
 struct ResidentState {
-    // ---- per schedule: follows the level lists of one stm_build_schedule.  `gen` is the stmmqr_plan::sched_gen the tables and the
+    // ---- per schedule: follows the level lists of one schedule (stmmqr_plan::sch).  `gen` is the stmmqr_plan::sched_gen the tables and the
     // static maps were built from (ensure_rowmap rebuilds them when the plan's has moved on); rm_gen / rmt_gen the same for the
-    // parts that the first product with R / with R' adds.  The planner itself writes the scratch layout (stmmqr_schedule.cpp).
+    // parts that the first product with R / with R' adds.
     struct Schedule {
         long gen = -1, rm_gen = -1, rmt_gen = -1, rjt_gen = -1;   // (rjt_gen: the transpose of Rj alone, ensure_rj_transpose)
         restab::LevelTables T;                          // dynamic LDS per level, split fronts, T4 bookkeeping, buffer sizes
@@ -35,9 +35,9 @@ struct ResidentState {
         DevBuf<int> d_t4fronts, d_Dq4;
         DevBuf<long long> d_t4dqo, d_qbt4off;
         DevBuf<double> d_T4;
-        // slab recycling: the scratch that holds the widest tree level (scr_doubles) or, scr_all, every front in front form
-        long long scr_doubles = 0;
-        std::vector<FrontSym> fs_scr;                   // FrontSym with foff into that scratch (kept fronts: their own slab, relative to it)
+        // slab recycling: the scratch that holds the widest tree level (the schedule's scr_doubles) or, scr_all, every front in front form
+        std::vector<FrontSym> fs_scr;                   // FrontSym with foff into that scratch: the schedule's fs_scr or the scr_all layout
+                                                        //  (ensure_scratch; kept fronts: their own slab, relative to it)
         bool scr_all = false;
         DevBuf<double> d_scr;
         DevBuf<FrontSym> d_fs_scr;

@@ -7,11 +7,6 @@
 
 #include "stmmqr_device.h"
 
-struct Level {                           // tree level of a group: what the solve / Q-apply kernels walk (f1)
-    int all_off = 0, n_all = 0;          // every front of the level (small first, then big by npanels desc)
-    int n_small = 0, n_big = 0;
-};
-
 namespace restab {
 // per level: the fronts that take the split Q-apply / back substitution (descriptors from `off`), their maxima, their T4 groups
 struct QbLevel { int off = 0, n = 0, max_np = 0, max_nslab = 0, max_fm = 0, max_rsteps = 0, t4i_off = 0, t4i_n = 0; };

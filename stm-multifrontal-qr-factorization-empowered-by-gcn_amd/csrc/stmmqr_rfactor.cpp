@@ -17,10 +17,10 @@ static_assert(sizeof(restab::T4Item) == sizeof(Qt4ItemHost) && offsetof(restab::
 // The FrontSym array those kernels read (host copy): fs, or with recycling fs_scr with the kept fronts rebased
 std::vector<FrontSym> resident_front_syms(const stmmqr_plan &P)
 {
-    if (!P.recycle) return P.fs;
+    if (!P.sch.recycle) return P.sch.fs;
     std::vector<FrontSym> t = P.res.sched.fs_scr;
     for (long f = 0; f < P.nf; f++)
-        if (P.kept[(size_t)f]) t[(size_t)f].foff = (long long)((P.d_F.p + P.fs[f].foff) - P.res.sched.d_scr.p);
+        if (P.sch.kept[(size_t)f]) t[(size_t)f].foff = (long long)((P.d_F.p + P.sch.fs[f].foff) - P.res.sched.d_scr.p);
     return t;
 }
 // ... and who may cut that array back to a view that ends at column ncol of a plan of [A B] (the carried solve, the covariance): the
@@ -39,21 +39,21 @@ int check_carried_view(const stmmqr_plan &P, long ncol)
 // does the plan hold the whole tree in one group (what the condition estimate and the selected inversion ask)
 bool holds_whole_tree(const stmmqr_plan &P)
 {
-    bool whole = P.glevels.size() == 1;
+    bool whole = P.sch.glevels.size() == 1;
     for (long f = 0; f < P.nf && whole; f++) whole = P.group[(size_t)f] == 0 && !((size_t)f < P.shared.size() && P.shared[(size_t)f]);
     return whole;
 }
 DevCtx res_ctx(stmmqr_plan &P)
 {
     DevCtx c = P.ctx();
-    if (P.recycle) { c.fs = P.res.sched.d_fs_scr.p; c.Farena = P.res.sched.d_scr.p; }
+    if (P.sch.recycle) { c.fs = P.res.sched.d_fs_scr.p; c.Farena = P.res.sched.d_scr.p; }
     return c;
 }
 int level_to_front_form(stmmqr_plan &P, size_t l)
 {
-    if (!P.recycle) return 0;
+    if (!P.sch.recycle) return 0;
     const auto &S = P.res.sched;
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     const DevCtx c = P.ctx();
     // staged blocks back in front form: R+H by k_rh_unpack, R only (keepH = 0) by k_rh_unpack's zero fill + k_r_unpack
     auto unpack = [&](const int *flist, int nfr) -> int {
@@ -63,7 +63,7 @@ int level_to_front_form(stmmqr_plan &P, size_t l)
     if (S.scr_all) {
         if (P.res.fact.scr_valid) return 0;
         // every front at once, kept until the next factorization (marked valid only once the launch was accepted)
-        const int e = unpack(P.d_lists.p + P.own_off, P.n_own);
+        const int e = unpack(P.d_lists.p + P.sch.own_off, P.sch.n_own);
         P.res.fact.scr_valid = (e == 0);
         return e;
     }
@@ -102,7 +102,7 @@ namespace {
 int ensure_scratch(stmmqr_plan &P)
 {
     auto &S = P.res.sched;
-    if (!P.recycle || (S.d_scr.p && S.d_fs_scr.p)) return 0;
+    if (!P.sch.recycle || (S.d_scr.p && S.d_fs_scr.p)) return 0;
     // Two layouts.  Where HBM has room (all recycled slabs within a quarter of what is free; STMMQR_RESIDENT_CACHE=0 / 1 forces) the
     // scratch holds EVERY front in front form, rebuilt once per factorization at the first Q-apply / solve and kept for the
     // following ones: the memory comes back only while the factors are being used, never during the factorization.  Otherwise it
@@ -110,16 +110,17 @@ int ensure_scratch(stmmqr_plan &P)
     size_t freeb = 0, totalb = 0;
     HIPCHK(hipMemGetInfo(&freeb, &totalb));
     long long all = 0;
-    for (long f = 0; f < P.nf; f++) if (!P.kept[(size_t)f]) all += (long long)P.fs[f].ld * P.fs[f].fn;
+    for (long f = 0; f < P.nf; f++) if (!P.sch.kept[(size_t)f]) all += (long long)P.sch.fs[f].ld * P.sch.fs[f].fn;
     const long cache = knobs::num(knobs::K_RESIDENT_CACHE);
     S.scr_all = cache >= 0 ? cache != 0 : (8.0 * (double)all <= 0.25 * (double)freeb);
+    S.fs_scr = P.sch.fs_scr;                                     // (the schedule's layout: one tree level at a time)
     if (S.scr_all) {
         long long o = 0;
         for (long f = 0; f < P.nf; f++)
-            if (!P.kept[(size_t)f]) { S.fs_scr[(size_t)f].foff = o; o += (long long)P.fs[f].ld * P.fs[f].fn; }
+            if (!P.sch.kept[(size_t)f]) { S.fs_scr[(size_t)f].foff = o; o += (long long)P.sch.fs[f].ld * P.sch.fs[f].fn; }
     }
     P.res.new_factorization();                                   // (nothing in the new scratch is in front form)
-    LCHK(S.d_scr.alloc((size_t)std::max(1LL, S.scr_all ? all : S.scr_doubles)));
+    LCHK(S.d_scr.alloc((size_t)std::max(1LL, S.scr_all ? all : P.sch.scr_doubles)));
     LCHK(S.d_fs_scr.upload(resident_front_syms(P), P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));
     return 0;
@@ -138,7 +139,7 @@ int map_rows_of_factorization(stmmqr_plan &P)
         HIPCHK(hipMemcpyAsync(P.h_fnum.data(), P.d_fnum.p, (size_t)nf * sizeof(FrontNum), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     std::vector<int> W, rb;
-    restab::row_map(P.Sleft, P.Hip, hii32, P.fs, P.h_fnum, P.m, P.n, W, rb);
+    restab::row_map(P.Sleft, P.Hip, hii32, P.sch.fs, P.h_fnum, P.m, P.n, W, rb);
     LCHK(P.res.fact.d_Wmap.upload(W, st));
     LCHK(P.res.fact.d_rowbase.upload(rb, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -166,7 +167,7 @@ int build_resident_tables(stmmqr_plan &P)
     LCHK(K.d_Xs.alloc((size_t)std::max(1L, n)));
     LCHK(K.d_Io.alloc((size_t)std::max(1L, std::max(m, n))));
     LCHK(K.d_err.alloc(1));
-    S.T = restab::level_tables(P.fs, P.glevels[0], P.lists, stm_qt4_doubles());
+    S.T = restab::level_tables(P.sch.fs, P.sch.glevels[0], P.sch.lists, stm_qt4_doubles());
     S.t4_ok = false; S.t4_tried = false; P.res.fact.t4_valid = false;
     LCHK(K.d_Xf.alloc((size_t)S.T.xf_doubles));
     LCHK(S.d_Dq.alloc((size_t)S.T.dq_ints));
@@ -191,7 +192,7 @@ int ensure_rowmap(stmmqr_plan &P)
         if (P.group[f] < 0) return fail(STMMQR_ERR_INVALID, "Q-apply / solve need every front on this device");
     PASS(map_rows_of_factorization(P));
     if (S.gen != P.sched_gen) PASS(build_resident_tables(P));
-    if (restab::live_counts(S.T, P.fs, P.h_fnum, knobs::on(knobs::K_LIVE_PANELS), P.res.fact.live))
+    if (restab::live_counts(S.T, P.sch.fs, P.h_fnum, knobs::on(knobs::K_LIVE_PANELS), P.res.fact.live))
         HIPCHK(hipMemcpy(S.d_qb.p, S.T.qb.data(), S.T.qb.size() * sizeof(QbDesc), hipMemcpyHostToDevice));
     // (the planner sends such fronts to the split kernels, so neither can happen; no launch may ask for more LDS than configured)
     for (int b : S.T.lds_qa)
@@ -289,7 +290,7 @@ int run_qapply(stmmqr_plan &P, int method, int nb = 1)
     const RhsBatch B = rhs_strides(P);
     DevCtx c = res_ctx(P);
     const int *L0 = P.d_lists.p;
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     // blocked form with the kept T factors; STMMQR_DBG bit 13 selects the reflector-by-reflector kernel (same result up
     // to rounding: used by the tests to cross-check the two)
     const bool blocked = c.Tall && !(c.dbg & 8192);
@@ -357,7 +358,7 @@ template <class Hook> int r_pass(stmmqr_plan &P, const DevCtx &c, int nb, Hook b
     const auto &K = P.res.call;
     const RhsBatch B = rhs_strides(P);
     const int *L0 = P.d_lists.p;
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     for (size_t l = LV.size(); l-- > 0;) {
         LCHK(level_to_front_form(P, l));
         LCHK(before_level(l));
@@ -420,7 +421,7 @@ int rt_pass(stmmqr_plan &P, int nb, RtMode mode)
     const RhsBatch B = rhs_strides(P);
     DevCtx c = res_ctx(P);
     const int *L0 = P.d_lists.p, *rowbase = P.res.fact.d_rowbase.p;
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     HIPCHK(hipMemsetAsync(K.d_Xr.p, 0, (size_t)nb * (size_t)std::max(1L, P.m) * sizeof(double), P.stream));
     for (size_t l = 0; l < LV.size(); l++) {
         const auto &R = S.T.rtbig[l];
@@ -454,13 +455,13 @@ int rt_vectors(stmmqr_plan &P, const double *Z, double *Y, int nb, bool through_
 int ensure_rmult(stmmqr_plan &P)
 {
     auto &S = P.res.sched;
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     if (S.rm_gen == P.sched_gen) return 0;
     S.rm_rslab.assign(LV.size(), 0);
     S.rm_cslab.assign(LV.size(), 0);
     for (size_t l = 0; l < LV.size(); l++)
         for (int q = 0; q < LV[l].n_all; q++) {
-            const FrontSym &s = P.fs[P.lists[LV[l].all_off + q]];
+            const FrontSym &s = P.sch.fs[P.sch.lists[LV[l].all_off + q]];
             S.rm_rslab[l] = std::max(S.rm_rslab[l], (std::min(s.fp, s.fm_ub) + STM_RM_ROWS - 1) / STM_RM_ROWS);
             S.rm_cslab[l] = std::max(S.rm_cslab[l], (s.fn + STM_RM_COLS - 1) / STM_RM_COLS);
         }
@@ -497,7 +498,7 @@ int rmult_pass(stmmqr_plan &P, const double *X, double *Y, int nb, int twofold)
     const auto &S = P.res.sched;
     const RhsBatch B = rhs_strides(P);
     const DevCtx c = res_ctx(P);
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     HIPCHK(hipMemsetAsync(Y, 0, (size_t)nb * (size_t)std::max(1L, P.m) * sizeof(double), P.stream));
     for (size_t l = 0; l < LV.size(); l++) {
         LCHK(level_to_front_form(P, l));
@@ -514,7 +515,7 @@ int rtmult_pass(stmmqr_plan &P, const double *Y, double *Z, int nb, int absval)
     double *U = P.res.call.d_U.p;
     const RhsBatch B = rhs_strides(P);
     const DevCtx c = res_ctx(P);
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     for (size_t l = 0; l < LV.size(); l++) {
         LCHK(level_to_front_form(P, l));
         LCHK(stm_launch_rtmult_dots(c, P.d_lists.p + LV[l].all_off, LV[l].n_all, S.rm_cslab[l], P.res.fact.d_rowbase.p, Y, U, absval, P.stream, nb, B));
@@ -664,7 +665,7 @@ int stmmqr_plan_solve_carried(stmmqr_plan *plan, stm_long nrhs, double *X, stm_l
     // ---- the view: FrontSym of the array the resident-factor kernels read (res_ctx) with fp cut back, the B fronts level by level ----
     std::vector<FrontSym> vs = resident_front_syms(P);
     std::vector<int> blist, boff;
-    restab::carried_view(P.fs, P.glevels[0], P.lists, n, vs, blist, boff);
+    restab::carried_view(P.sch.fs, P.sch.glevels[0], P.sch.lists, n, vs, blist, boff);
     if (K.d_fs_car.n != vs.size()) LCHK(K.d_fs_car.alloc(vs.size()));
     if (K.d_carlist.n < blist.size()) LCHK(K.d_carlist.alloc(blist.size()));
     if (!vs.empty()) HIPCHK(hipMemcpyAsync(K.d_fs_car.p, vs.data(), vs.size() * sizeof(FrontSym), hipMemcpyHostToDevice, st));

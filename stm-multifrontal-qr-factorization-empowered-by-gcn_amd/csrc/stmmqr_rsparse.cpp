@@ -59,7 +59,7 @@ int stmmqr_plan_r_sparse(stmmqr_plan *plan, int form, stm_long ncol, stm_long ec
     long long rtot = 0;
     for (long f = 0; f < P.nf; f++) rtot += P.h_fnum[(size_t)f].rank;
     const DevCtx c = res_ctx(P);
-    const auto &LV = P.glevels[0];
+    const auto &LV = P.sch.glevels[0];
     const int *dRj = S.d_Rj.p, *rowbase = P.res.fact.d_rowbase.p;
     int *cnt = csc ? S.d_rsSlot.p : S.d_rsRow.p;
     int *vis = cnt + (csc ? std::max(1L, P.rjsize) : std::max(1L, m));

@@ -30,15 +30,15 @@ struct Run {
     hipStream_t st = P.stream;
     DevCtx c = P.ctx(k.dbg);
     const int *L0 = P.d_lists.p;
-    const std::vector<Step> &SV = P.gsteps[grp];
+    const std::vector<Step> &SV = P.sch.gsteps[grp];
     long nlaunch = 0;
     int cur_step = 0;
     const Step *pend = nullptr;                                // passengers: the step whose k_upd_c beyond block 0 is still due
 
     const int *act(const Step &S) const { return L0 + S.act_off; }
     const int *pl(const Step &S) const { return L0 + S.plist_off; }
-    const FrontSym &front(const Step &S, int i) const { return P.fs[P.lists[S.act_off + i]]; }
-    int panel(const Step &S, int i) const { return P.lists[S.plist_off + i]; }
+    const FrontSym &front(const Step &S, int i) const { return P.sch.fs[P.sch.lists[S.act_off + i]]; }
+    int panel(const Step &S, int i) const { return P.sch.lists[S.plist_off + i]; }
     // the epoch of a step's hand-offs through global memory (k_upd_f, k_upd_b0w): the step number of the group
     int epoch(const Step &S) const { return (int)(&S - SV.data()) + 1 + grp * (1 << 20); }
     // tiles (256 x 32) of the update beyond block 0 of the step's normal fronts (expected rows, not the bound)
@@ -66,7 +66,7 @@ struct Run {
         for (int i = 0; i < S.n_act; i++) rows = std::max(rows, stm_panel_rows_est(front(S, i), panel(S, i)));
         return rows;
     }
-    bool packs(const Step &S) const { return S.n_cpk > 0 || (P.recycle && S.n_rhp > 0); }
+    bool packs(const Step &S) const { return S.n_cpk > 0 || (P.sch.recycle && S.n_rhp > 0); }
 
     template <class F> int timed(int cat, F &&fn)
     {
@@ -92,7 +92,7 @@ struct Run {
         const int *starting = L0 + S.start_off;
         if (S.n_start > 0) {
             PASS(timed(CAT_ASM, [&]() -> int {
-                if (P.recycle) { LCHK(stm_launch_zero_slabs(c, starting, S.n_start, S.asm_maxparts, q)); nlaunch++; }
+                if (P.sch.recycle) { LCHK(stm_launch_zero_slabs(c, starting, S.n_start, S.asm_maxparts, q)); nlaunch++; }
                 LCHK(stm_launch_setup(c, starting, S.n_start, q));
                 LCHK(stm_launch_assemble(c, starting, L0 + S.asm_parts_off, S.n_start, S.asm_maxparts, q));
                 return 0;
@@ -159,18 +159,18 @@ struct Run {
                 // panel r of a sweep of w: column blocks 0 .. w-1-r (the columns of the next panels), T by the Gram block; after the
                 // last one the w panels at once on everything beyond
                 int o = S.n_norm;
-                for (int r = 0; r < P.sweep; r++) {
+                for (int r = 0; r < P.sch.sweep; r++) {
                     const int n = S.n_pk[r];
                     if (n <= 0) continue;
-                    LCHK(stm_launch_update_split(c, act + o, pl + o, n, 0, P.sweep - r, S.maxsl_pk[r], Wp, wl + o, wcnt, 1, q));
+                    LCHK(stm_launch_update_split(c, act + o, pl + o, n, 0, P.sch.sweep - r, S.maxsl_pk[r], Wp, wl + o, wcnt, 1, q));
                     nlaunch += 2;
-                    if (r == P.sweep - 1) {
+                    if (r == P.sch.sweep - 1) {
                         if (c.dbg & 65536)                     // tests: the sweep launches by front, with the front's own column blocks
                             for (int i = 0; i < n; i++)
-                                fprintf(stderr, "[sweep launch] w %d step %d front %d panel %d ncbp %d nslf %d (launch: ncbp %d maxsl %d)\n", P.sweep,
-                                        cur_step, P.lists[S.act_off + o + i], panel(S, o + i), stm_upd_ncb(front(S, o + i), panel(S, o + i)) - 1,
+                                fprintf(stderr, "[sweep launch] w %d step %d front %d panel %d ncbp %d nslf %d (launch: ncbp %d maxsl %d)\n", P.sch.sweep,
+                                        cur_step, P.sch.lists[S.act_off + o + i], panel(S, o + i), stm_upd_ncb(front(S, o + i), panel(S, o + i)) - 1,
                                         stm_upd_nsl(front(S, o + i)), S.maxcbp_po, S.maxsl_pk[r]);
-                        if (P.sweep == 4) LCHK(stm_launch_update_quad(c, act + o, pl + o, n, S.maxcbp_po, S.maxsl_pk[r], Wp, wl + o, wcnt, q));
+                        if (P.sch.sweep == 4) LCHK(stm_launch_update_quad(c, act + o, pl + o, n, S.maxcbp_po, S.maxsl_pk[r], Wp, wl + o, wcnt, q));
                         else LCHK(stm_launch_update_pair(c, act + o, pl + o, n, S.maxcbp_po, S.maxsl_pk[r], Wp, wl + o, wcnt, q));
                         nlaunch += 3;
                     }
@@ -199,7 +199,7 @@ struct Run {
         if (!packs(S)) return 0;
         return timed(CAT_CPK, [&]() -> int {
             if (S.n_cpk > 0) { LCHK(stm_launch_cpack(c, L0 + S.cpk_off, L0 + S.cpk_parts_off, S.n_cpk, S.cpk_maxparts, q)); nlaunch++; }
-            if (P.recycle && S.n_rhp > 0) {
+            if (P.sch.recycle && S.n_rhp > 0) {
                 // slab recycling: the packed R+H blocks of the fronts that are finished now go to the arena (sizes and places on the
                 // device: k_rh_count bumps the arena's pointer); their slabs are free from the next step on
                 if (P.keep_h) {
@@ -270,7 +270,7 @@ struct Run {
     {
         long pwg = 0;
         for (int i = 0; i < S.n_act; i++)
-            pwg += stm_use_ca(front(S, i), panel(S, i), P.plan_algo, P.ca_min) ? stm_ca_slabs(front(S, i)) : stm_tall_launches(front(S, i), panel(S, i), P.tall_min);
+            pwg += stm_use_ca(front(S, i), panel(S, i), P.sch.plan_algo, P.sch.ca_min) ? stm_ca_slabs(front(S, i)) : stm_tall_launches(front(S, i), panel(S, i), P.sch.tall_min);
         return S.n_sweep() == 0 &&                                  // (pair-update steps stay on one stream)
                tiles_beyond_b0(S) >= (b0_fused(S) ? std::min(k.la_min, k.la_min_fused) : k.la_min) && pwg <= k.la_maxpwg;
     }
@@ -311,7 +311,7 @@ struct Run {
             prep_on_side = false;
             if (S.n_act > 0) PASS(panels(S));
             // (early end: a front may end at a panel with trailing columns; its step is packed after the whole update)
-            const bool offload = S.n_act > 0 && S.maxcb > 1 && worth_it(S) && !(P.early_end && packs(S));
+            const bool offload = S.n_act > 0 && S.maxcb > 1 && worth_it(S) && !(P.sch.early_end && packs(S));
             if (!offload) {
                 if (S.n_act > 0) {
                     PASS(join_side());
@@ -449,7 +449,7 @@ struct Run {
                     PASS(update(S, 0, S.maxcb, true, P.d_Wp.p, st));
             }
             // (a front that ends at a panel with trailing columns -- FrontSym::nsched -- is packed only after the riders of that update)
-            if (pend && P.early_end && packs(S)) PASS(flush_alone());
+            if (pend && P.sch.early_end && packs(S)) PASS(flush_alone());
             PASS(post(S, st));
         }
         return flush_alone();
@@ -478,7 +478,7 @@ int stm_ensure_la_events(stmmqr_plan &P, size_t nsteps, const knobs::RunKnobs &k
 
 int stm_run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req)
 {
-    if (grp < 0 || grp >= (int)P.gsteps.size()) return fail(STMMQR_ERR_INVALID, "no such front group");
+    if (grp < 0 || grp >= (int)P.sch.gsteps.size()) return fail(STMMQR_ERR_INVALID, "no such front group");
     Run R{P, detail, grp};
     if (req) {
         R.c.cbskip = std::max(1, req->cb_stride) - 1;
@@ -491,8 +491,8 @@ int stm_run_schedule(stmmqr_plan &P, bool detail, int grp, const StepReq *req)
     const bool la = g_opt.lookahead && !pass && !detail && !P.serial_panels && R.SV.size() > 1 && R.any_step_worth_it();
     PASS(pass ? R.run_passengers() : la ? R.run_lookahead() : R.run_serial());
     P.stats.nlaunch += R.nlaunch;
-    P.stats.nlevels += (long)P.glevels[grp].size();
-    P.stats.nsteps += (long)P.gsteps[grp].size();
+    P.stats.nlevels += (long)P.sch.glevels[grp].size();
+    P.stats.nsteps += (long)P.sch.gsteps[grp].size();
     return 0;
 }
 
@@ -505,11 +505,11 @@ int stm_run_pack(stmmqr_plan &P, bool &overflow)
     hipStream_t st = P.stream;
     const DevCtx c = P.ctx();
     const int *L0 = P.d_lists.p;
-    if (P.recycle) {
+    if (P.sch.recycle) {
         // the blocks were staged front by front (Run::post); what is left are the kept fronts' column offsets, the
         // reference's layout of all blocks (Post order: d_fin, used by the download) and the check that the arena held everything
         std::vector<int> kl;
-        for (long f = 0; f < P.nf; f++) if (P.kept[(size_t)f]) kl.push_back((int)f);
+        for (long f = 0; f < P.nf; f++) if (P.sch.kept[(size_t)f]) kl.push_back((int)f);
         if (!kl.empty()) {
             DevBuf<int> d_kl;
             LCHK(d_kl.upload(kl, st));
@@ -518,7 +518,7 @@ int stm_run_pack(stmmqr_plan &P, bool &overflow)
             LCHK(P.keep_h ? stm_launch_rh_count(ck, d_kl.p, (int)kl.size(), st) : stm_launch_r_count(ck, d_kl.p, (int)kl.size(), st));
             HIPCHK(hipStreamSynchronize(st));
         }
-        LCHK(stm_launch_rh_scan(c, L0 + P.post_off, (int)P.nf, P.d_total.p, P.d_fin.p, st));
+        LCHK(stm_launch_rh_scan(c, L0 + P.sch.post_off, (int)P.nf, P.d_total.p, P.d_fin.p, st));
         long long total = 0, top[2] = {0, 0};
         HIPCHK(hipMemcpyAsync(&total, P.d_total.p, sizeof(long long), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(top, P.d_rhtop.p, 2 * sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -528,15 +528,15 @@ int stm_run_pack(stmmqr_plan &P, bool &overflow)
         overflow = (top[1] != 0);
         return 0;
     }
-    LCHK(P.keep_h ? stm_launch_rh_count(c, L0 + P.own_off, P.n_own, st) : stm_launch_r_count(c, L0 + P.own_off, P.n_own, st));
-    LCHK(stm_launch_rh_scan(c, L0 + P.post_off, (int)P.nf, P.d_total.p, P.d_Rboff.p, st));
+    LCHK(P.keep_h ? stm_launch_rh_count(c, L0 + P.sch.own_off, P.sch.n_own, st) : stm_launch_r_count(c, L0 + P.sch.own_off, P.sch.n_own, st));
+    LCHK(stm_launch_rh_scan(c, L0 + P.sch.post_off, (int)P.nf, P.d_total.p, P.d_Rboff.p, st));
     long long total = 0;
     HIPCHK(hipMemcpyAsync(&total, P.d_total.p, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     P.rh_total = total;
     if ((size_t)total > P.d_RH.n) LCHK(P.d_RH.alloc((size_t)(total + total / 64 + 1024)));   // (a little room: a refactorization with other dead columns)
-    if (P.keep_h) LCHK(stm_launch_rh_copy(c, L0 + P.own_off, L0 + P.rh_parts_off, P.n_own, P.rh_maxparts, P.d_RH.p, st));
-    else LCHK(stm_launch_r_copy(c, L0 + P.own_off, L0 + P.rh_parts_off, P.n_own, P.rh_maxparts, P.d_RH.p, st));
+    if (P.keep_h) LCHK(stm_launch_rh_copy(c, L0 + P.sch.own_off, L0 + P.sch.rh_parts_off, P.sch.n_own, P.sch.rh_maxparts, P.d_RH.p, st));
+    else LCHK(stm_launch_r_copy(c, L0 + P.sch.own_off, L0 + P.sch.rh_parts_off, P.sch.n_own, P.sch.rh_maxparts, P.d_RH.p, st));
     P.stats.nlaunch += 3;
     return 0;
 }

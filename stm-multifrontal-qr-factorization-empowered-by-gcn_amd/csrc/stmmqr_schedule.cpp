@@ -1,93 +1,132 @@
-// stmmqr_schedule.cpp -- the planner's schedule: arenas, the timeline allocator of the slab recycling and build_schedule, the
-// step timeline of every front group.  Everything here is symbolic; what it builds is run by stmmqr_run.cpp.
+// stmmqr_schedule.cpp -- the planner (stmmqr_sched.h): the symbolic sizes of the fronts, and sched::build -- arenas, the timeline
+// allocator of the slab recycling, the step timeline of every front group.  Everything here is symbolic and pure: values in, a value
+// out; stm_install_schedule (stmmqr_planbuild.cpp) puts it into a plan, stmmqr_run.cpp runs it.
 //
-// level schedule.  P.group[f] = g >= 0: front f is factorized here in phase g; -1: not on this device (its
+// level schedule.  in.group[f] = g >= 0: front f is factorized here in phase g; -1: not on this device (its
 // contribution block is imported).  For every group the fronts are bucketed by tree level (leaves = 0, counted
 // inside the group), small ones first, large ones by decreasing panel count.
-#include "stmmqr_plan.h"
+#include "stmmqr_sched.h"
+
+#include <algorithm>
 
 static_assert(STM_CA_MIN_ROWS == 4096, "the default of STMMQR_CA_MIN (stmmqr_knobs.h) is the kernels' STM_CA_MIN_ROWS");
 
-// Offsets of the fronts (F arena) and of the packed contribution blocks (C arena) for the CURRENT groups: a front gets room
-// in F when it is factorized here (group >= 0), a contribution block when its front is factorized here or arrives here
-// (stmmqr_plan_import_front: a child of one of this plan's fronts).  One rank of a sharded run holds its subtrees and the
-// fronts above them that it owns or shares, not the whole tree.  (Every front keeps its F until the factors are packed at the
-// end of the factorization: stmmqr_factorize_finish.)
-void stm_assign_arenas(stmmqr_plan &P)
-{
-    long long foff = 0, coff = 0;
-    std::vector<char> needc((size_t)std::max(1L, P.nf), 0);
-    P.c_slot.assign((size_t)std::max(1L, P.nf), 0);
-    for (long f = 0; f < P.nf; f++) {
-        if (P.group[f] < 0) continue;
-        needc[(size_t)f] = 1;
-        for (long q = P.Childp[f]; q < P.Childp[f + 1]; q++) needc[(size_t)P.Child[q]] = 1;
-    }
-    for (long kf = 0; kf < P.nf; kf++) {
-        const long f = P.Post[kf];
-        FrontSym &s = P.fs[f];
-        s.foff = 0; s.coff = 0;
-        if (P.group[f] >= 0) {
-            s.foff = foff;
-            foff += (long long)s.ld * s.fn;
-        }
-        if (needc[(size_t)f]) {
-            const long cn = s.fn - s.fp, fm = s.fm_ub;
-            const long cm = P.do_rank ? std::min(fm, cn) : std::min(std::max(fm - std::min(fm, (long)s.fp), 0L), cn);
-            s.coff = coff;
-            P.c_slot[(size_t)f] = (long long)cm * (cm + 1) / 2 + (long long)cm * (cn - cm);
-            coff += P.c_slot[(size_t)f];
-            coff = (coff + 1) & ~1LL;
-        }
-    }
-    P.has_c.swap(needc);
-    P.farena = std::max(1LL, foff); P.carena = std::max(1LL, coff);
-}
+namespace sched {
 
-// the arenas themselves: (re)allocated when their size changed (first factorization of a plan, or after a regrouping)
-int stm_ensure_arenas(stmmqr_plan &P)
+// ---- per-front symbolic sizes -----------------------------------------------------------
+int front_syms(const Symbolic &v, Fronts &out, std::string &msg)
 {
-    if (P.d_F.p && P.d_F.n == (size_t)P.farena && P.d_C.p && P.d_C.n == (size_t)P.carena &&
-        (!P.recycle || (P.d_RH.p && P.d_RH.n == (size_t)P.rh_cap)))
-        return 0;
-    HIPCHK(hipStreamSynchronize(P.stream));
-    if (P.d_F.n != (size_t)P.farena) P.d_F.release();
-    if (P.d_C.n != (size_t)P.carena) P.d_C.release();
-    size_t freeb = 0, totalb = 0;
-    HIPCHK(hipMemGetInfo(&freeb, &totalb));
-    const double need = 8.0 * ((P.d_F.p ? 0.0 : (double)P.farena) + (P.d_C.p ? 0.0 : (double)P.carena) +
-                               ((P.recycle && P.d_RH.n != (size_t)P.rh_cap) ? (double)P.rh_cap : 0.0)) * 1.02;
-    if (need > 0.95 * (double)freeb) return fail(STMMQR_ERR_OUT_OF_MEMORY, "front arena does not fit in free HBM");
-    if (!P.d_F.p) LCHK(P.d_F.alloc((size_t)P.farena));
-    if (!P.d_C.p) LCHK(P.d_C.alloc((size_t)P.carena));
-    if (P.recycle && P.d_RH.n != (size_t)P.rh_cap) LCHK(P.d_RH.alloc((size_t)P.rh_cap));
+    const long nf = v.nf;
+    std::vector<long> parent(nf, -1);
+    for (long f = 0; f < nf; f++)
+        for (long q = v.Childp[f]; q < v.Childp[f + 1]; q++) parent[v.Child[q]] = f;
+
+    // upper bound on the rows of every front: taken from the analysis when given (QRsym->Fm, worst case when
+    // rank detection is on: SparseQR_analyze.c:461-471), otherwise recomputed with the same recurrence
+    out.Fm.assign(nf, 0);
+    if (v.Fm) {
+        for (long f = 0; f < nf; f++) out.Fm[f] = v.Fm[f];
+    } else {
+        std::vector<long> cmub(nf, 0);
+        for (long kf = 0; kf < nf; kf++) {
+            const long f = v.Post[kf];
+            const long fp = v.Super[f + 1] - v.Super[f], fn = v.Rp[f + 1] - v.Rp[f];
+            long fm = v.Sleft[v.Super[f + 1]] - v.Sleft[v.Super[f]];
+            for (long q = v.Childp[f]; q < v.Childp[f + 1]; q++) fm += cmub[v.Child[q]];
+            out.Fm[f] = fm;
+            const long cn = fn - fp;
+            cmub[f] = v.do_rank ? std::min(fm, cn) : std::min(std::max(fm - std::min(fm, fp), 0L), cn);
+        }
+    }
+
+    // the row count every front will have if no pivot column dies (exact for full-rank input): used only to plan the
+    // number of panel launches (stm_tall_panel); the kernels cope with any actual row count
+    std::vector<long> &fmest = out.fm_est, &cmest = out.cm_est;
+    fmest.assign(nf, 0); cmest.assign(nf, 0);
+    for (long kf = 0; kf < nf; kf++) {
+        const long f = v.Post[kf];
+        const long fp = v.Super[f + 1] - v.Super[f], fn = v.Rp[f + 1] - v.Rp[f];
+        long fe = v.Sleft[v.Super[f + 1]] - v.Sleft[v.Super[f]];
+        for (long q = v.Childp[f]; q < v.Childp[f + 1]; q++) fe += cmest[v.Child[q]];
+        fmest[f] = std::min(fe, out.Fm[f]);
+        cmest[f] = std::min(std::max(fe - std::min(fe, fp), 0L), fn - fp);
+    }
+
+    out.fs.assign(nf, FrontSym());
+    long long tpan_total = 0;
+    for (long kf = 0; kf < nf; kf++) {
+        const long f = v.Post[kf];
+        FrontSym &s = out.fs[f];
+        const long fp = v.Super[f + 1] - v.Super[f], fn = v.Rp[f + 1] - v.Rp[f];
+        const long fm = out.Fm[f];
+        // (front-local offsets are 64-bit on the device: row + column * ld; rows and columns themselves are int32)
+        if (fm * fn >= (1L << 36)) { msg = "a single front exceeds 2^36 entries"; return 1; }
+        s.fn = (int)fn; s.fp = (int)fp; s.col1 = (int)v.Super[f]; s.rp = (int)v.Rp[f]; s.hip = (int)v.Hip[f];
+        s.child0 = (int)v.Childp[f]; s.child1 = (int)v.Childp[f + 1];
+        s.srow0 = (int)v.Sleft[v.Super[f]]; s.srow1 = (int)v.Sleft[v.Super[f + 1]];
+        s.fm_ub = (int)fm;
+        s.fm_est = (int)fmest[f];
+        s.ld = (int)std::max(2L, (fm + 1) & ~1L);
+        s.npanels = (int)((fn + STM_NB - 1) / STM_NB);
+        s.tpan = (int)tpan_total;
+        tpan_total += s.npanels;
+        // Q-apply: fronts with this many entries or more are split over workgroups (k_qbig_*); STMMQR_QBIG_MIN
+        // overrides the threshold (tests send small fronts through that path).  2 M entries until round 4; with the grouped launches
+        // (k_qbig_step4) smaller fronts pay too, at 256 KB of T4 per four panels -- default workload, threshold: Q'b / solve ms,
+        // GB of T4: 2 M 13.1 / 20.6, 0.31; 1 M 12.5 / 20.0, 0.39; 256 K 11.9 / 19.5, 0.61; 128 K 11.6 / 19.2, 0.81.  1 M.
+        // ... and, whatever its entry count, a front that one workgroup cannot hold in LDS: a tall thin one (16 363 rows at 40
+        // columns) or a short wide one whose columns are all pivotal (10 921 of them) -- the split kernels have no such limit
+        const bool over_lds = stm_lds_qapply(fm, fn) > STM_RES_LDS_MAX || stm_lds_rsolve(fp, fn) > STM_RES_LDS_MAX;
+        s.qbig = ((fm * fn >= v.qbig_min || over_lds) && fn >= 1) ? 1 : 0;
+        // R' x = b: the one-workgroup kernel keeps the front's u and x in LDS (6 550 columns of a square-ish front, 10 890 of a
+        // short wide one); a front beyond that is split over its columns (k_rtbig_*) by the pass that knows how, rt_pass in mode RT_SPLIT.
+        // STMMQR_RTBIG_MIN splits smaller ones too
+        s.rtbig = (stm_lds_rtsolve(fp, fm, fn) > STM_RES_LDS_MAX || fm * fn >= v.rtbig_min) ? 1 : 0;
+        s.parent = (int)parent[f];
+        s.foff = 0; s.coff = 0;                                    // (they belong to a schedule: Planner::assign_arenas)
+    }
+    out.tpanels = tpan_total;
     return 0;
 }
 
-// device side of the slab recycling of the current schedule (after stm_build_schedule): kept flags, scratch layout, bump words
-int stm_upload_recycle(stmmqr_plan &P)
+// ---- size of every packed R+H block if no pivot column dies (exact for full-rank input): the symbolic staircase of the front
+// (qr_fsize: rows of S by leftmost column + the children's contribution rows, whose leftmost columns are the columns of their
+// C) run through qr_front's row bookkeeping (:1434-1609) and qr_rhpack's column lengths (:1691-1784).  Sizes the R+H arena of
+// the slab recycling (with a margin; QRsym->maxstack is the hard bound the arena falls back to) ----
+void rh_estimate(const Symbolic &v, const std::vector<int> &Rjrel, Fronts &out)
 {
-    if (!P.d_rhtop.p) LCHK(P.d_rhtop.alloc(2));
-    if (!P.d_fin.p || P.d_fin.n < (size_t)std::max(1L, P.nf)) LCHK(P.d_fin.alloc((size_t)std::max(1L, P.nf)));
-    HIPCHK(hipMemsetAsync(P.d_rhtop.p, 0, 2 * sizeof(long long), P.stream));
-    if (!P.recycle) return 0;
-    LCHK(P.d_kept.upload(P.kept, P.stream));
-    HIPCHK(hipStreamSynchronize(P.stream));
-    P.res.sched.d_scr.release();                                     // (allocated by the first resident-factor operation: ensure_scratch)
-    P.d_RH.release();                                         // (the arena follows with the front arenas: stm_ensure_arenas)
-    return 0;
+    const long nf = v.nf;
+    out.rh_est_total = 0;
+    out.rh_est_front.assign((size_t)std::max(1L, nf), 0);
+    std::vector<long> stair;
+    for (long kf = 0; kf < nf; kf++) {
+        const long f = v.Post[kf];
+        const long fp = out.fs[f].fp, fn = out.fs[f].fn, fm = out.fm_est[f];
+        stair.assign((size_t)fn + 1, 0);
+        for (long j = 0; j < fp; j++) stair[(size_t)j] = v.Sleft[v.Super[f] + j + 1] - v.Sleft[v.Super[f] + j];
+        for (long q = v.Childp[f]; q < v.Childp[f + 1]; q++) {
+            const long c = v.Child[q];
+            const long fpc = v.Super[c + 1] - v.Super[c], pc = v.Rp[c] + fpc;
+            for (long i = 0; i < out.cm_est[c]; i++) stair[(size_t)Rjrel[(size_t)(pc + i)]]++;
+        }
+        long run = 0;
+        for (long j = 0; j < fn; j++) { run += stair[(size_t)j]; stair[(size_t)j] = run; }       // rows with leftmost column <= j
+        long g = 0, rm = 0;
+        long long sz = 0;
+        for (long k = 0; k < fn; k++) {
+            long t;
+            if (g >= fm) t = (k < fp) ? 0 : fm;                       // rows ran out
+            else { t = std::min(fm, std::max(g + 1, stair[(size_t)k])); g++; }
+            if (!v.keep_h) { if (k < fp && t > 0 && rm < fm) rm++; sz += rm; continue; }   // (R only: rm rows per column)
+            if (k < fp) { if (t > 0) rm++; sz += (t > 0) ? t : rm; }
+            else { const long h = std::min(rm + (k - fp) + 1, fm); sz += rm + std::max(t - h, 0L); }
+        }
+        out.rh_est_total += sz;
+        out.rh_est_front[(size_t)f] = sz;
+    }
 }
 
-namespace {
-
-const int LDS_CAP_DOUBLES = STM_LDS_CAP_DOUBLES;   // 128 KiB of dynamic LDS for the staged (sub-)panel, k_panel
-const int LDS_CAP_SMALL = 15360;          // 120 KiB in k_front_wg (it carries 8 KiB more static LDS)
-
-// ---- timeline allocator (slab recycling) ----------------------------------------------------------------------------------
-// Objects with a size and a lifetime [t0, t1] in steps; an address may be given to another object from step t1 + 1 on.  Objects
-// are placed in order of their first step (larger first inside a step) at the lowest address that holds them (address-ordered
-// first fit, free blocks coalesced).  Returns the peak address.  Everything is symbolic, so the offsets are part of the plan.
-struct TlObj { long long size; int t0, t1; long long *out; };
+// the timeline allocator of the slab recycling (stmmqr_sched.h says what it does)
 long long timeline_first_fit(std::vector<TlObj> &objs, long long base, int nstep)
 {
     std::vector<std::vector<int>> at0((size_t)nstep + 1), at1((size_t)nstep + 2);
@@ -139,31 +178,10 @@ long long timeline_first_fit(std::vector<TlObj> &objs, long long base, int nstep
     return peak;
 }
 
-// Front and contribution-block offsets of a plan that holds the whole tree in ONE group, from the step timeline of that group
-// (P.f_t0 / f_t1 / c_t1, filled by Planner::recycling_layout).  `kept` fronts sit at the bottom of the front arena for good.
-// Returns {front arena, contribution arena} in doubles.
-std::pair<long long, long long> timeline_offsets(stmmqr_plan &P, const std::vector<char> &kept, int nstep, bool apply)
-{
-    const long nf = P.nf;
-    std::vector<long long> foff((size_t)std::max(1L, nf), 0), coff((size_t)std::max(1L, nf), 0);
-    long long base = 0;
-    for (long f = 0; f < nf; f++)
-        if (kept[(size_t)f]) { foff[(size_t)f] = base; base += (long long)P.fs[f].ld * P.fs[f].fn; }
-    std::vector<TlObj> fo, co;
-    for (long f = 0; f < nf; f++) {
-        const FrontSym &s = P.fs[f];
-        if (!kept[(size_t)f]) fo.push_back({(long long)s.ld * s.fn, P.f_t0[f], P.f_t1[f], &foff[(size_t)f]});
-        const long cn = s.fn - s.fp, fm = s.fm_ub;
-        const long cm = P.do_rank ? std::min(fm, cn) : std::min(std::max(fm - std::min(fm, (long)s.fp), 0L), cn);
-        const long long csz = (long long)cm * (cm + 1) / 2 + (long long)cm * (cn - cm);
-        if (apply) P.c_slot[(size_t)f] = csz;
-        co.push_back({csz, P.f_t1[f], std::max(P.f_t1[f], P.c_t1[f]), &coff[(size_t)f]});
-    }
-    const long long fpeak = timeline_first_fit(fo, base, nstep), cpeak = timeline_first_fit(co, 0, nstep);
-    if (apply)
-        for (long f = 0; f < nf; f++) { P.fs[f].foff = foff[(size_t)f]; P.fs[f].coff = coff[(size_t)f]; }
-    return {std::max(1LL, fpeak), std::max(1LL, cpeak)};
-}
+namespace {
+
+const int LDS_CAP_DOUBLES = STM_LDS_CAP_DOUBLES;   // 128 KiB of dynamic LDS for the staged (sub-)panel, k_panel
+const int LDS_CAP_SMALL = 15360;          // 120 KiB in k_front_wg (it carries 8 KiB more static LDS)
 
 // the step timeline of one group while it is being built
 struct Timeline {
@@ -175,50 +193,78 @@ struct Timeline {
     std::vector<std::vector<int>> small_at, starting, ending;  // ... the fronts that start at t / are packed at the end of t
 };
 
-// build_schedule: the phases below, called in sequence by stm_build_schedule.  The order of what they append to P.lists and
-// P.wlists is part of the plan: offsets into both are baked into every Step.
+// sched::build: the phases below, called in sequence.  The order of what they append to out.lists and
+// out.wlists is part of the plan: offsets into both are baked into every Step.
 struct Planner {
-    stmmqr_plan &P;
-    std::vector<int> &tslot;
-    const knobs::BuildKnobs k = knobs::BuildKnobs::read();
-    const long nf = P.nf;
+    const Inputs &in;
+    Schedule out;
+    const knobs::BuildKnobs &k = in.k;
+    const long nf = in.nf;
     int ngroups = 1;
     bool whole = false;          // ONE group holds every front and none is shared
 
-    bool shared(long f) const { return (size_t)f < P.shared.size() && P.shared[(size_t)f]; }
-    bool is_big(int f) const
-    {
-        const FrontSym &s = P.fs[f];
-        return s.fn >= g_opt.big_front_cols && s.fm_ub >= 64;
-    }
+    bool shared(long f) const { return (size_t)f < in.shared.size() && in.shared[(size_t)f]; }
+    bool is_big(int f) const { return sched::is_big(out.fs[f], in.opt.big_front_cols); }
     // Pair update (k_upd_w2 / k_upd_c2): a property of the front alone -- it changes the rounding of the front's
     // trailing updates, and results must not depend on the schedule.  Fronts whose update is bandwidth bound: many rows.
     bool is_pair(int f) const
     {
-        const FrontSym &s = P.fs[f];
+        const FrontSym &s = out.fs[f];
         if (shared(f)) return false;                              // (the pair update has no column-block stride)
-        return g_opt.pair_update && is_big(f) && s.fm_est >= k.pair_min && s.npanels >= 4;
+        return in.opt.pair_update && is_big(f) && s.fm_est >= k.pair_min && s.npanels >= 4;
     }
-    int steps_of(int f) const { return is_big(f) ? P.fs[f].nsched : 1; }
+    int steps_of(int f) const { return is_big(f) ? out.fs[f].nsched : 1; }
     // workgroups a front gets in the assembly / packing launches for `work` entries
-    static int work_parts(long work)
-    {
-        const long pg = knobs::once<knobs::K_PART_GRAIN>(), pc = knobs::once<knobs::K_PART_CAP>();
-        return (int)std::min(pc, std::max(1L, (work + pg - 1) / pg));
-    }
+    int work_parts(long work) const { return (int)std::min(in.part_cap, std::max(1L, (work + in.part_grain - 1) / in.part_grain)); }
     // ... in the copy of its packed R+H block (a wave per column; 64 left the 17.6 GB copy of a 50 000-column front at 0.5 TB/s)
     static int rh_parts(const FrontSym &s) { return std::min(256, std::max(1, s.fn / 16)); }
 
     void begin()
     {
-        P.sched_gen++;
-        P.tune = k.tune;
-        P.tall_min = g_opt.tall_min_rows;
-        P.plan_algo = g_opt.panel_algo;
-        P.ca_min = k.ca_min;
-        for (long f = 0; f < nf; f++) ngroups = std::max(ngroups, P.group[f] + 1);
+        out.fs = in.fs;
+        out.tune = k.tune;
+        out.tall_min = in.opt.tall_min_rows;
+        out.plan_algo = in.opt.panel_algo;
+        out.ca_min = k.ca_min;
+        for (long f = 0; f < nf; f++) ngroups = std::max(ngroups, in.group[f] + 1);
         whole = (ngroups == 1) && nf > 0;
-        for (long f = 0; f < nf && whole; f++) whole = (P.group[f] == 0) && !shared(f);
+        for (long f = 0; f < nf && whole; f++) whole = (in.group[f] == 0) && !shared(f);
+    }
+
+    // Offsets of the fronts (F arena) and of the packed contribution blocks (C arena) for the groups: a front gets room
+    // in F when it is factorized here (group >= 0), a contribution block when its front is factorized here or arrives here
+    // (stmmqr_plan_import_front: a child of one of this plan's fronts).  One rank of a sharded run holds its subtrees and the
+    // fronts above them that it owns or shares, not the whole tree.  (Every front keeps its F until the factors are packed at the
+    // end of the factorization: stmmqr_factorize_finish.  A plan that recycles gets other offsets: recycling_layout.)
+    void assign_arenas()
+    {
+        long long foff = 0, coff = 0;
+        std::vector<char> needc((size_t)std::max(1L, in.nf), 0);
+        out.c_slot.assign((size_t)std::max(1L, in.nf), 0);
+        for (long f = 0; f < in.nf; f++) {
+            if (in.group[f] < 0) continue;
+            needc[(size_t)f] = 1;
+            for (long q = in.Childp[f]; q < in.Childp[f + 1]; q++) needc[(size_t)in.Child[q]] = 1;
+        }
+        for (long kf = 0; kf < in.nf; kf++) {
+            const long f = in.Post[kf];
+            FrontSym &s = out.fs[f];
+            s.foff = 0; s.coff = 0;
+            if (in.group[f] >= 0) {
+                s.foff = foff;
+                foff += (long long)s.ld * s.fn;
+            }
+            if (needc[(size_t)f]) {
+                const long cn = s.fn - s.fp, fm = s.fm_ub;
+                const long cm = in.do_rank ? std::min(fm, cn) : std::min(std::max(fm - std::min(fm, (long)s.fp), 0L), cn);
+                s.coff = coff;
+                out.c_slot[(size_t)f] = (long long)cm * (cm + 1) / 2 + (long long)cm * (cn - cm);
+                coff += out.c_slot[(size_t)f];
+                coff = (coff + 1) & ~1LL;
+            }
+        }
+        out.has_c.swap(needc);
+        out.farena = std::max(1LL, foff); out.carena = std::max(1LL, coff);
     }
 
     // slab recycling: plans that hold the whole tree in one group (STMMQR_RECYCLE=0: every front keeps its slab, as sharded
@@ -226,35 +272,35 @@ struct Planner {
     void decide_recycle()
     {
         long long slabs = 0;
-        for (long f = 0; f < nf; f++) slabs += (long long)P.fs[f].ld * P.fs[f].fn;
-        P.recycle = whole && !P.rec.overflowed && k.recycles(slabs);
+        for (long f = 0; f < nf; f++) slabs += (long long)out.fs[f].ld * out.fs[f].fn;
+        out.recycle = whole && !in.overflowed && k.recycles(slabs);
     }
 
     void mark_pair_fronts()
     {
-        P.sweep = (g_opt.pair_update == 4) ? 4 : 2;
-        P.pair_front.assign(std::max(1L, nf), 0);
-        for (long f = 0; f < nf; f++) P.pair_front[f] = (P.group[f] >= 0 && is_pair((int)f)) ? 1 : 0;
-        P.ypoff.assign(std::max(1L, nf), -1);
-        P.yp_doubles = 0;
+        out.sweep = (in.opt.pair_update == 4) ? 4 : 2;
+        out.pair_front.assign(std::max(1L, nf), 0);
+        for (long f = 0; f < nf; f++) out.pair_front[f] = (in.group[f] >= 0 && is_pair((int)f)) ? 1 : 0;
+        out.ypoff.assign(std::max(1L, nf), -1);
+        out.yp_doubles = 0;
         for (long f = 0; f < nf; f++)
-            if (P.pair_front[f]) {
-                P.ypoff[f] = P.yp_doubles;
-                P.yp_doubles += (long long)((P.fs[f].fn + 31) / 32) * (P.sweep * STM_NB * 32);
+            if (out.pair_front[f]) {
+                out.ypoff[f] = out.yp_doubles;
+                out.yp_doubles += (long long)((out.fs[f].fn + 31) / 32) * (out.sweep * STM_NB * 32);
             }
     }
 
     void clear_lists()
     {
-        tslot.assign(std::max(1L, nf), 0);
-        P.glevels.assign(ngroups, std::vector<Level>());
-        P.gsteps.assign(ngroups, std::vector<Step>());
-        P.lists.clear();
-        P.wlists.clear();
-        P.tslots = 1;
-        P.gp_slabs = 1;
-        P.wp_doubles = 0;
-        P.wp2_doubles = 0;
+        out.tslot.assign(std::max(1L, nf), 0);
+        out.glevels.assign(ngroups, std::vector<Level>());
+        out.gsteps.assign(ngroups, std::vector<Step>());
+        out.lists.clear();
+        out.wlists.clear();
+        out.tslots = 1;
+        out.gp_slabs = 1;
+        out.wp_doubles = 0;
+        out.wp2_doubles = 0;
     }
 
     // ---- how many panels of a front get a step (FrontSym::nsched).  A front of fm rows and fn > fm columns runs out of rows at
@@ -264,18 +310,18 @@ struct Planner {
     // the device, but fm_est -- the rows if no pivot column dies -- is exact for a full-rank matrix: a plan that holds the whole tree
     // schedules floor(min(fm_est, fn) / 32) + 1 panels per front.  Should a front NOT be finished by its last scheduled panel
     // (pivot columns died below it: more rows reach it than estimated), k_cpack's extra workgroup raises abort[2] and the
-    // factorization is run again on the full schedule, which the plan then keeps (P.rec.full_schedule; stats.retries counts it).
+    // factorization is run again on the full schedule, which the plan then keeps (in.full_schedule; stats.retries counts it).
     // STMMQR_EARLY_END=0: every panel a step, as before. ----
     void cut_fronts()
     {
-        const bool early = (whole || P.rec.early_phased) && !P.rec.full_schedule && k.early_end;
+        const bool early = (whole || in.early_phased) && !in.full_schedule && k.early_end;
         for (long f = 0; f < nf; f++) {
-            FrontSym &s = P.fs[f];
+            FrontSym &s = out.fs[f];
             s.nsched = s.npanels;
-            if (early && is_big((int)f) && !is_pair((int)f) && P.group[f] >= 0 && !shared(f))
+            if (early && is_big((int)f) && !is_pair((int)f) && in.group[f] >= 0 && !shared(f))
                 s.nsched = std::min(s.npanels, std::min(s.fm_est, s.fn) / STM_NB + 1 + k.early_slack);
         }
-        P.early_end = early;
+        out.early_end = early;
     }
 
     // ---- tree levels (leaves = 0, counted inside the group): the order of the solves and of Q; the first and last step of every
@@ -286,12 +332,12 @@ struct Planner {
         level.assign(nf, -1); start.assign(nf, 0); end.assign(nf, 0);
         int nlev = 0, nstep = 0;
         for (long kf = 0; kf < nf; kf++) {
-            const long f = P.Post[kf];
-            if (P.group[f] != grp) continue;
+            const long f = in.Post[kf];
+            if (in.group[f] != grp) continue;
             int lv = 0, t0 = 0;
-            for (long q = P.Childp[f]; q < P.Childp[f + 1]; q++) {
-                const long ch = P.Child[q];
-                if (P.group[ch] != grp) continue;              // (earlier phase or imported: already there)
+            for (long q = in.Childp[f]; q < in.Childp[f + 1]; q++) {
+                const long ch = in.Child[q];
+                if (in.group[ch] != grp) continue;              // (earlier phase or imported: already there)
                 lv = std::max(lv, level[ch] + 1);
                 t0 = std::max(t0, end[ch]);
             }
@@ -309,8 +355,8 @@ struct Planner {
             for (int lv = 0; lv < nlev; lv++) {
                 int e1 = lvl_end[lv];
                 for (long kf = 0; kf < nf; kf++) {
-                    const long f = P.Post[kf];
-                    if (P.group[f] != grp || level[f] != lv) continue;
+                    const long f = in.Post[kf];
+                    if (in.group[f] != grp || level[f] != lv) continue;
                     lstart[f] = lvl_end[lv];
                     lend[f] = lstart[f] + steps_of((int)f);
                     e1 = std::max(e1, lend[f]);
@@ -334,18 +380,18 @@ struct Planner {
         T.nlev = nlev; T.nstep = nstep;
         std::vector<std::vector<int>> byl(nlev);
         for (long kf = 0; kf < nf; kf++)
-            if (P.group[P.Post[kf]] == grp) byl[level[P.Post[kf]]].push_back((int)P.Post[kf]);
-        std::vector<Level> &LV = P.glevels[grp];
+            if (in.group[in.Post[kf]] == grp) byl[level[in.Post[kf]]].push_back((int)in.Post[kf]);
+        std::vector<Level> &LV = out.glevels[grp];
         LV.assign(nlev, Level());
         for (int lv = 0; lv < nlev; lv++) {
             Level &L = LV[lv];
             std::vector<int> small, big;
             for (int f : byl[lv]) (is_big(f) ? big : small).push_back(f);
-            std::stable_sort(big.begin(), big.end(), [&](int a, int b) { return P.fs[a].npanels > P.fs[b].npanels; });
-            L.all_off = (int)P.lists.size();
+            std::stable_sort(big.begin(), big.end(), [&](int a, int b) { return out.fs[a].npanels > out.fs[b].npanels; });
+            L.all_off = (int)out.lists.size();
             L.n_small = (int)small.size(); L.n_big = (int)big.size(); L.n_all = L.n_small + L.n_big;
-            P.lists.insert(P.lists.end(), small.begin(), small.end());
-            P.lists.insert(P.lists.end(), big.begin(), big.end());
+            out.lists.insert(out.lists.end(), small.begin(), small.end());
+            out.lists.insert(out.lists.end(), big.begin(), big.end());
         }
     }
 
@@ -362,27 +408,27 @@ struct Planner {
             panel_at.assign(T.nstep, {});
             small_at.assign(T.nstep, {});
             for (long kf = 0; kf < nf; kf++) {
-                const int f = (int)P.Post[kf];
-                if (P.group[f] != grp) continue;
+                const int f = (int)in.Post[kf];
+                if (in.group[f] != grp) continue;
                 if (!is_big(f)) { small_at[T.start[f]].push_back(f); continue; }
-                for (int q = 0; q < P.fs[f].nsched; q++) panel_at[T.start[f] + q].push_back({f, q});
+                for (int q = 0; q < out.fs[f].nsched; q++) panel_at[T.start[f] + q].push_back({f, q});
             }
             return;
         }
         std::vector<int> parent_in(nf, -1), pend(nf, 0), tails(nf, 0);
         for (long f = 0; f < nf; f++) {
-            if (P.group[f] != grp) continue;
-            for (long q = P.Childp[f]; q < P.Childp[f + 1]; q++)
-                if (P.group[P.Child[q]] == grp) { parent_in[P.Child[q]] = (int)f; pend[f]++; }
+            if (in.group[f] != grp) continue;
+            for (long q = in.Childp[f]; q < in.Childp[f + 1]; q++)
+                if (in.group[in.Child[q]] == grp) { parent_in[in.Child[q]] = (int)f; pend[f]++; }
         }
         for (long kf = nf; kf-- > 0;) {
-            const long f = P.Post[kf];
-            if (P.group[f] != grp) continue;
+            const long f = in.Post[kf];
+            if (in.group[f] != grp) continue;
             tails[f] = steps_of((int)f) + (parent_in[f] >= 0 ? tails[parent_in[f]] : 0);
         }
         std::vector<int> ready;
         for (long kf = 0; kf < nf; kf++)
-            if (P.group[P.Post[kf]] == grp && pend[P.Post[kf]] == 0) ready.push_back((int)P.Post[kf]);
+            if (in.group[in.Post[kf]] == grp && pend[in.Post[kf]] == 0) ready.push_back((int)in.Post[kf]);
         struct Fly { int f, p; };
         std::vector<Fly> fly;                                 // big fronts ready or in flight, with their next panel
         while (!ready.empty() || !fly.empty()) {
@@ -399,7 +445,7 @@ struct Planner {
             };
             if (!fly.empty()) {
                 auto rem = [&](const Fly &e) { return tails[e.f] - e.p; };
-                auto rows = [&](const Fly &e) { return stm_panel_rows_est(P.fs[e.f], e.p); };
+                auto rows = [&](const Fly &e) { return stm_panel_rows_est(out.fs[e.f], e.p); };
                 int rl = 0, env = 0;
                 for (const Fly &e : fly) rl = std::max(rl, rem(e));
                 for (const Fly &e : fly)
@@ -408,7 +454,7 @@ struct Planner {
                 for (Fly &e : fly) {
                     if (rem(e) == rl || rows(e) <= k.ride * env) {
                         panel_at.back().push_back({e.f, e.p});
-                        if (++e.p >= P.fs[e.f].nsched) { finish(e.f); continue; }
+                        if (++e.p >= out.fs[e.f].nsched) { finish(e.f); continue; }
                     }
                     keep.push_back(e);
                 }
@@ -433,7 +479,7 @@ struct Planner {
             for (int f : T.small_at[t]) starting[t].push_back(f);
             for (const auto &fp : T.panel_at[t]) {
                 if (fp.second == 0) starting[t].push_back(fp.first);
-                if (fp.second == P.fs[fp.first].nsched - 1) ending[t].push_back(fp.first);
+                if (fp.second == out.fs[fp.first].nsched - 1) ending[t].push_back(fp.first);
             }
         }
         // The packing of finished fronts is batched: k_cpack runs at the last step before some front STARTS (only an
@@ -449,7 +495,7 @@ struct Planner {
             carry_from = (flush || ending[t].empty()) ? -1 : t;
             if (!flush && !ending[t].empty()) carry_from = t;
         }
-        std::vector<Step> &SV = P.gsteps[grp];
+        std::vector<Step> &SV = out.gsteps[grp];
         SV.assign(nstep, Step());
         std::vector<int> active, freeslots;                   // big fronts in flight; released T / Gram slots
         int nslots = 0;
@@ -457,16 +503,16 @@ struct Planner {
             Step &S = SV[t];
             std::vector<int> small, big;
             for (int f : starting[t]) (is_big(f) ? big : small).push_back(f);
-            S.start_off = (int)P.lists.size();
+            S.start_off = (int)out.lists.size();
             S.n_small = (int)small.size(); S.n_start = (int)(small.size() + big.size());
-            P.lists.insert(P.lists.end(), small.begin(), small.end());
-            P.lists.insert(P.lists.end(), big.begin(), big.end());
-            S.asm_parts_off = (int)P.lists.size();
+            out.lists.insert(out.lists.end(), small.begin(), small.end());
+            out.lists.insert(out.lists.end(), big.begin(), big.end());
+            S.asm_parts_off = (int)out.lists.size();
             long maxfm_small = 0;
             for (int i = 0; i < S.n_start; i++) {
-                const FrontSym &s = P.fs[P.lists[S.start_off + i]];
+                const FrontSym &s = out.fs[out.lists[S.start_off + i]];
                 const int parts = work_parts((long)s.fm_ub * s.fn);
-                P.lists.push_back(parts);
+                out.lists.push_back(parts);
                 S.asm_maxparts = std::max(S.asm_maxparts, parts);
                 if (i < S.n_small) maxfm_small = std::max(maxfm_small, (long)s.fm_ub);
             }
@@ -477,39 +523,39 @@ struct Planner {
             if (S.n_small > 0) S.lds_small = std::max(S.lds_small, STM_NB * 128 + 64);
             // T / Gram-partial slots: a slot is held from the step a front starts to the step it ends
             for (int f : big) {
-                if (!freeslots.empty()) { tslot[f] = freeslots.back(); freeslots.pop_back(); }
-                else tslot[f] = nslots++;
+                if (!freeslots.empty()) { out.tslot[f] = freeslots.back(); freeslots.pop_back(); }
+                else out.tslot[f] = nslots++;
             }
             active.clear();
             for (const auto &fp : T.panel_at[t]) { active.push_back(fp.first); pan_now[fp.first] = fp.second; }
             // heaviest update first (the order inside a launch does not change any result); classes: see Step
-            auto work_at = [&](int f) { return (long)stm_upd_ncb(P.fs[f], pan_now[f]) * stm_upd_nsl(P.fs[f]); };
-            auto cls = [&](int f) { return !is_pair(f) ? 0 : 1 + pan_now[f] % P.sweep; };
+            auto work_at = [&](int f) { return (long)stm_upd_ncb(out.fs[f], pan_now[f]) * stm_upd_nsl(out.fs[f]); };
+            auto cls = [&](int f) { return !is_pair(f) ? 0 : 1 + pan_now[f] % out.sweep; };
             std::stable_sort(active.begin(), active.end(), [&](int a, int b) {
                 return cls(a) != cls(b) ? cls(a) < cls(b) : work_at(a) > work_at(b);
             });
-            S.act_off = (int)P.lists.size();
+            S.act_off = (int)out.lists.size();
             S.n_act = (int)active.size();
-            P.lists.insert(P.lists.end(), active.begin(), active.end());
-            S.plist_off = (int)P.lists.size();
-            for (int f : active) P.lists.push_back(pan_now[f]);
-            S.wp_off = (int)P.wlists.size();
+            out.lists.insert(out.lists.end(), active.begin(), active.end());
+            S.plist_off = (int)out.lists.size();
+            for (int f : active) out.lists.push_back(pan_now[f]);
+            S.wp_off = (int)out.wlists.size();
             long long wp = 0, ncbsum = 0;
             long maxfm_big = 0;
             for (int f : active) {
-                const FrontSym &s = P.fs[f];
+                const FrontSym &s = out.fs[f];
                 const int p = pan_now[f];
                 const int ncb = stm_upd_ncb(s, p), nsl = stm_upd_nsl(s);
-                const bool ca = stm_use_ca(s, p, g_opt.panel_algo, P.ca_min), tall = stm_tall_panel(s, p, P.tall_min);
-                P.wlists.push_back(wp);
+                const bool ca = stm_use_ca(s, p, in.opt.panel_algo, out.ca_min), tall = stm_tall_panel(s, p, out.tall_min);
+                out.wlists.push_back(wp);
                 // (+1: Gram block.  Pair-update fronts: two blocks per partial, at most stm_pair_slots partials per column block in the
                 //  sweep of an odd panel -- a workgroup takes up to four slabs --, and the panel-by-panel updates of the next panels'
                 //  columns use the first 2 + 1 column blocks with the full slab count)
                 //  (quad update: four blocks per partial, three Gram blocks, 4 + 1 column blocks in the panel-by-panel updates)
                 if (is_pair(f))
-                    wp += std::max((long long)(ncb + P.sweep - 1) * (P.sweep == 4 ? stm_quad_slots(nsl, P.tune) : stm_pair_slots(nsl, P.tune)) *
-                                       (P.sweep * STM_NB * 32),
-                                   (P.sweep + 1LL) * nsl * (STM_NB * 32));
+                    wp += std::max((long long)(ncb + out.sweep - 1) * (out.sweep == 4 ? stm_quad_slots(nsl, out.tune) : stm_pair_slots(nsl, out.tune)) *
+                                       (out.sweep * STM_NB * 32),
+                                   (out.sweep + 1LL) * nsl * (STM_NB * 32));
                 else
                     wp += (long long)(ncb + 1) * nsl * (STM_NB * 32);
                 const int c = cls(f);
@@ -521,12 +567,12 @@ struct Planner {
                 } else {
                     S.n_pk[c - 1]++;
                     S.maxsl_pk[c - 1] = std::max(S.maxsl_pk[c - 1], nsl);
-                    if (c == P.sweep) S.maxcbp_po = std::max(S.maxcbp_po, ncb - 1);
+                    if (c == out.sweep) S.maxcbp_po = std::max(S.maxcbp_po, ncb - 1);
                 }
-                S.nsub = std::max(S.nsub, stm_tall_launches(s, p, P.tall_min));
+                S.nsub = std::max(S.nsub, stm_tall_launches(s, p, out.tall_min));
                 S.nca = std::max(S.nca, stm_ca_slabs(s));
                 (ca ? S.nca_use : S.npipe_use)++;
-                P.gp_slabs = std::max(P.gp_slabs, stm_ca_slabs(s));
+                out.gp_slabs = std::max(out.gp_slabs, stm_ca_slabs(s));
                 maxfm_big = std::max(maxfm_big, (long)s.fm_ub);
                 if (!tall && !ca) S.lds_plan = std::max(S.lds_plan, stm_front_lds(s));
                 // a short panel of the pipeline is taken by one workgroup with the panel's image in LDS (dev_wave_panel)
@@ -537,23 +583,48 @@ struct Planner {
             // form's redundant T (every column-block workgroup builds it) costs throughput (T is built once per front
             // by k_upd_w).  Either form gives the same bits.
             S.split = (S.maxsl >= 3 || ncbsum >= 512) ? 1 : 0;
-            P.wp_doubles = std::max(P.wp_doubles, wp);
-            if (S.n_sweep() == 0) P.wp2_doubles = std::max(P.wp2_doubles, wp);
+            out.wp_doubles = std::max(out.wp_doubles, wp);
+            if (S.n_sweep() == 0) out.wp2_doubles = std::max(out.wp2_doubles, wp);
             // fronts at their last panel: packed at the end of the step, slot released for the next
-            S.cpk_off = (int)P.lists.size();
+            S.cpk_off = (int)out.lists.size();
             S.n_cpk = (int)ending[t].size();
-            P.lists.insert(P.lists.end(), ending[t].begin(), ending[t].end());
-            S.cpk_parts_off = (int)P.lists.size();
+            out.lists.insert(out.lists.end(), ending[t].begin(), ending[t].end());
+            S.cpk_parts_off = (int)out.lists.size();
             for (int f : ending[t]) {
-                const FrontSym &s = P.fs[f];
+                const FrontSym &s = out.fs[f];
                 const long cn = s.fn - s.fp;
                 const int parts = work_parts(cn * std::min((long)s.fm_ub, cn));
-                P.lists.push_back(parts);
+                out.lists.push_back(parts);
                 S.cpk_maxparts = std::max(S.cpk_maxparts, parts);
-                freeslots.push_back(tslot[f]);
+                freeslots.push_back(out.tslot[f]);
             }
         }
-        P.tslots = std::max(P.tslots, nslots);
+        out.tslots = std::max(out.tslots, nslots);
+    }
+
+    // Front and contribution-block offsets of a plan that holds the whole tree in ONE group, from the step timeline of that group
+    // (out.f_t0 / f_t1 / c_t1, filled by Planner::recycling_layout).  `kept` fronts sit at the bottom of the front arena for good.
+    // Returns {front arena, contribution arena} in doubles.
+    std::pair<long long, long long> timeline_offsets(const std::vector<char> &kept, int nstep, bool apply)
+    {
+            std::vector<long long> foff((size_t)std::max(1L, nf), 0), coff((size_t)std::max(1L, nf), 0);
+        long long base = 0;
+        for (long f = 0; f < nf; f++)
+            if (kept[(size_t)f]) { foff[(size_t)f] = base; base += (long long)out.fs[f].ld * out.fs[f].fn; }
+        std::vector<TlObj> fo, co;
+        for (long f = 0; f < nf; f++) {
+            const FrontSym &s = out.fs[f];
+            if (!kept[(size_t)f]) fo.push_back({(long long)s.ld * s.fn, out.f_t0[f], out.f_t1[f], &foff[(size_t)f]});
+            const long cn = s.fn - s.fp, fm = s.fm_ub;
+            const long cm = in.do_rank ? std::min(fm, cn) : std::min(std::max(fm - std::min(fm, (long)s.fp), 0L), cn);
+            const long long csz = (long long)cm * (cm + 1) / 2 + (long long)cm * (cn - cm);
+            if (apply) out.c_slot[(size_t)f] = csz;
+            co.push_back({csz, out.f_t1[f], std::max(out.f_t1[f], out.c_t1[f]), &coff[(size_t)f]});
+        }
+        const long long fpeak = timeline_first_fit(fo, base, nstep), cpeak = timeline_first_fit(co, 0, nstep);
+        if (apply)
+            for (long f = 0; f < nf; f++) { out.fs[f].foff = foff[(size_t)f]; out.fs[f].coff = coff[(size_t)f]; }
+        return {std::max(1LL, fpeak), std::max(1LL, cpeak)};
     }
 
     // ---- slab recycling: lifetimes of the slabs and contribution blocks on this timeline, the fronts that keep their slab,
@@ -561,17 +632,17 @@ struct Planner {
     void recycling_layout(int grp, const Timeline &T)
     {
         const int nstep = T.nstep;
-        std::vector<Step> &SV = P.gsteps[grp];
-        const std::vector<Level> &LV = P.glevels[grp];
-        auto slab = [&](long f) { return (long long)P.fs[f].ld * P.fs[f].fn; };
-        P.f_t0.assign((size_t)std::max(1L, nf), 0); P.f_t1.assign((size_t)std::max(1L, nf), 0); P.c_t1.assign((size_t)std::max(1L, nf), 0);
+        std::vector<Step> &SV = out.gsteps[grp];
+        const std::vector<Level> &LV = out.glevels[grp];
+        auto slab = [&](long f) { return (long long)out.fs[f].ld * out.fs[f].fn; };
+        out.f_t0.assign((size_t)std::max(1L, nf), 0); out.f_t1.assign((size_t)std::max(1L, nf), 0); out.c_t1.assign((size_t)std::max(1L, nf), 0);
         for (int t = 0; t < nstep; t++) {
-            for (int f : T.starting[t]) { P.f_t0[(size_t)f] = t; if (!is_big(f)) P.f_t1[(size_t)f] = t; }
-            for (int f : T.ending[t]) P.f_t1[(size_t)f] = t;
+            for (int f : T.starting[t]) { out.f_t0[(size_t)f] = t; if (!is_big(f)) out.f_t1[(size_t)f] = t; }
+            for (int f : T.ending[t]) out.f_t1[(size_t)f] = t;
         }
         for (long f = 0; f < nf; f++) {
-            const int par = P.fs[f].parent;
-            P.c_t1[(size_t)f] = (par >= 0) ? P.f_t0[(size_t)par] : P.f_t1[(size_t)f];
+            const int par = out.fs[f].parent;
+            out.c_t1[(size_t)f] = (par >= 0) ? out.f_t0[(size_t)par] : out.f_t1[(size_t)f];
         }
         // which fronts keep their slab: none, or the 1-3 largest -- whatever makes fronts + contribution blocks + R+H arena
         // smallest (the arena holds min(maxstack, all recycled slabs) doubles: the reference's bound for all of R+H)
@@ -582,15 +653,15 @@ struct Planner {
         // front's R is packed on the fly by the download and never enters it
         auto staged_est = [&](const std::vector<char> &kp) -> long long {
             double e = 0;
-            for (long f = 0; f < nf; f++) if (!kp[(size_t)f]) e += (double)P.rh_est_front[(size_t)f];
-            const long long est = (long long)(e * P.rh_est_scale);
+            for (long f = 0; f < nf; f++) if (!kp[(size_t)f]) e += (double)in.rh_est_front[(size_t)f];
+            const long long est = (long long)(e * in.rh_est_scale);
             return est + est / 8 + 4096;
         };
         // the hard bound of the arena when the fronts in kp keep their slab
         auto hard_cap = [&](const std::vector<char> &kp) -> long long {
             long long rec = 0;
             for (long f = 0; f < nf; f++) if (!kp[(size_t)f]) rec += slab(f);
-            return (P.maxstack > 0) ? std::min((long long)P.maxstack, rec) : rec;
+            return (in.maxstack > 0) ? std::min((long long)in.maxstack, rec) : rec;
         };
         long long best = -1;
         int bestk = 0;
@@ -600,87 +671,86 @@ struct Planner {
         for (int q = 0; forced < 0 && q <= std::min(3L, nf); q++) {
             std::vector<char> kp((size_t)std::max(1L, nf), 0);
             for (int i = 0; i < q; i++) kp[(size_t)bysize[(size_t)i]] = 1;
-            const auto pk = timeline_offsets(P, kp, nstep, false);
+            const auto pk = timeline_offsets(kp, nstep, false);
             long long cap = hard_cap(kp);
-            if (!P.keep_h && !P.rec.rh_grow) cap = std::min(cap, staged_est(kp));     // (R only: the arena follows the packed R)
+            if (!in.keep_h && !in.rh_grow) cap = std::min(cap, staged_est(kp));     // (R only: the arena follows the packed R)
             const long long tot = pk.first + pk.second + cap;
             if (best < 0 || tot < best - best / 50) { best = tot; bestk = q; }      // (a kept front must buy at least 2 %)
         }
-        P.kept.assign((size_t)std::max(1L, nf), 0);
-        for (int i = 0; i < bestk; i++) P.kept[(size_t)bysize[(size_t)i]] = 1;
-        P.rh_cap = std::max(1LL, hard_cap(P.kept));
+        out.kept.assign((size_t)std::max(1L, nf), 0);
+        for (int i = 0; i < bestk; i++) out.kept[(size_t)bysize[(size_t)i]] = 1;
+        out.rh_cap = std::max(1LL, hard_cap(out.kept));
         // (the estimate + 12.5 % where that is less: dead columns move rows into later fronts and can make the factors
         //  larger than the full-rank pattern says; an arena that overflows is regrown to the hard bound and the factorization
         //  repeated once -- stats.retries says so)
-        if (!P.rec.rh_grow && !P.keep_h) P.rh_cap = std::max(1LL, std::min(P.rh_cap, staged_est(P.kept)));
-        else if (!P.rec.rh_grow && P.rh_est_total > 0) {
-            // (P.rh_est_scale: tests shrink the estimate to drive the overflow path)
-            const long long est = (long long)((double)P.rh_est_total * P.rh_est_scale);
-            P.rh_cap = std::max(1LL, std::min(P.rh_cap, est + est / 8 + 4096));
+        if (!in.rh_grow && !in.keep_h) out.rh_cap = std::max(1LL, std::min(out.rh_cap, staged_est(out.kept)));
+        else if (!in.rh_grow && in.rh_est_total > 0) {
+            // (in.rh_est_scale: tests shrink the estimate to drive the overflow path)
+            const long long est = (long long)((double)in.rh_est_total * in.rh_est_scale);
+            out.rh_cap = std::max(1LL, std::min(out.rh_cap, est + est / 8 + 4096));
         }
-        const auto pk = timeline_offsets(P, P.kept, nstep, true);
-        P.farena = pk.first; P.carena = pk.second;
-        P.has_c.assign((size_t)std::max(1L, nf), 1);
+        const auto pk = timeline_offsets(out.kept, nstep, true);
+        out.farena = pk.first; out.carena = pk.second;
+        out.has_c.assign((size_t)std::max(1L, nf), 1);
         for (int t = 0; t < nstep; t++) {
             Step &S = SV[t];
             std::vector<int> rhp;
-            for (int f : T.starting[t]) if (!is_big(f) && !P.kept[(size_t)f]) rhp.push_back(f);
-            for (int f : T.ending[t]) if (!P.kept[(size_t)f]) rhp.push_back(f);
-            S.rhp_off = (int)P.lists.size();
+            for (int f : T.starting[t]) if (!is_big(f) && !out.kept[(size_t)f]) rhp.push_back(f);
+            for (int f : T.ending[t]) if (!out.kept[(size_t)f]) rhp.push_back(f);
+            S.rhp_off = (int)out.lists.size();
             S.n_rhp = (int)rhp.size();
-            P.lists.insert(P.lists.end(), rhp.begin(), rhp.end());
-            S.rhp_parts_off = (int)P.lists.size();
+            out.lists.insert(out.lists.end(), rhp.begin(), rhp.end());
+            S.rhp_parts_off = (int)out.lists.size();
             for (int f : rhp) {
-                const int parts = rh_parts(P.fs[f]);
-                P.lists.push_back(parts);
+                const int parts = rh_parts(out.fs[f]);
+                out.lists.push_back(parts);
                 S.rhp_maxparts = std::max(S.rhp_maxparts, parts);
             }
         }
         // scratch of the resident-factor operations: every tree level in front form, one level at a time
-        ResidentState::Schedule &R = P.res.sched;
-        R.fs_scr = P.fs;
-        R.scr_doubles = 1;
+        out.fs_scr = out.fs;
+        out.scr_doubles = 1;
         for (size_t l = 0; l < LV.size(); l++) {
             long long o = 0;
             for (int q = 0; q < LV[l].n_all; q++) {
-                const int f = P.lists[(size_t)(LV[l].all_off + q)];
-                if (P.kept[(size_t)f]) continue;
-                R.fs_scr[(size_t)f].foff = o;
+                const int f = out.lists[(size_t)(LV[l].all_off + q)];
+                if (out.kept[(size_t)f]) continue;
+                out.fs_scr[(size_t)f].foff = o;
                 o += slab(f);
             }
-            R.scr_doubles = std::max(R.scr_doubles, o);
+            out.scr_doubles = std::max(out.scr_doubles, o);
         }
     }
 
     // fronts factorized on this device, in Post order, + their R+H copy parts; then ALL fronts in Post order
     void tail_lists()
     {
-        P.own_off = (int)P.lists.size();
-        P.n_own = 0;
+        out.own_off = (int)out.lists.size();
+        out.n_own = 0;
         for (long kf = 0; kf < nf; kf++)
-            if (P.group[P.Post[kf]] >= 0) { P.lists.push_back((int)P.Post[kf]); P.n_own++; }
-        P.rh_parts_off = (int)P.lists.size();
-        P.rh_maxparts = 1;
+            if (in.group[in.Post[kf]] >= 0) { out.lists.push_back((int)in.Post[kf]); out.n_own++; }
+        out.rh_parts_off = (int)out.lists.size();
+        out.rh_maxparts = 1;
         for (long kf = 0; kf < nf; kf++) {
-            if (P.group[P.Post[kf]] < 0) continue;
-            const int parts = rh_parts(P.fs[P.Post[kf]]);
-            P.lists.push_back(parts);
-            P.rh_maxparts = std::max(P.rh_maxparts, parts);
+            if (in.group[in.Post[kf]] < 0) continue;
+            const int parts = rh_parts(out.fs[in.Post[kf]]);
+            out.lists.push_back(parts);
+            out.rh_maxparts = std::max(out.rh_maxparts, parts);
         }
-        P.post_off = (int)P.lists.size();
-        for (long kf = 0; kf < nf; kf++) P.lists.push_back((int)P.Post[kf]);
-        if (P.lists.empty()) P.lists.push_back(0);
-        if (P.wlists.empty()) P.wlists.push_back(0);
-        P.h_tslot = tslot;
+        out.post_off = (int)out.lists.size();
+        for (long kf = 0; kf < nf; kf++) out.lists.push_back((int)in.Post[kf]);
+        if (out.lists.empty()) out.lists.push_back(0);
+        if (out.wlists.empty()) out.wlists.push_back(0);
     }
 };
 
 }  // namespace
 
-void stm_build_schedule(stmmqr_plan &P, std::vector<int> &tslot)
+Schedule build(const Inputs &in)
 {
-    Planner B{P, tslot};
+    Planner B{in, Schedule()};
     B.begin();
+    B.assign_arenas();
     B.decide_recycle();
     B.mark_pair_fronts();
     B.clear_lists();
@@ -690,7 +760,10 @@ void stm_build_schedule(stmmqr_plan &P, std::vector<int> &tslot)
         B.levels(grp, T);
         B.order_steps(grp, T);
         B.emit_steps(grp, T);
-        if (P.recycle && grp == 0) B.recycling_layout(grp, T);
+        if (B.out.recycle && grp == 0) B.recycling_layout(grp, T);
     }
     B.tail_lists();
+    return std::move(B.out);
 }
+
+}  // namespace sched
