@@ -804,7 +804,7 @@ int stmmqr_plan_export_r(stmmqr_plan *plan, const stm_qr_symbolic *sym, stm_long
  * < econ, columns < ncol), info[2] = the rows of R, info[3] = 0.  Complete on return (the plan's stream is synchronised).
  * Deterministic: positions come from scans and from ranks within a wave's ballot, no atomics -- the same bits run after run, and the
  * bits of stmmqr_plan_export_r.  ptr and every offset are 64-bit.
- * Reads R only: plans with and without H.  H itself is not exported here -- that stays with stmmqr_plan_export_r's host path.
+ * Reads R only: plans with and without H.  H, HTau and HPinv come out the same way through stmmqr_plan_h_sparse below.
  * Memory, made at the first call of a form and kept with the plan (a plan that never calls this allocates nothing for it): compressed
  * columns 16 bytes per entry of Rj (two int counts and a 64-bit offset per slot) and the transpose of Rj (4 bytes per entry + 4 per
  * column, shared with stmmqr_plan_rmult's trans = 1); compressed rows 8 bytes per row of the matrix.  With host arrays the device
@@ -818,6 +818,34 @@ int stmmqr_plan_r_sparse(stmmqr_plan *plan, int form, stm_long ncol, stm_long ec
                          stm_long *info /* [4], always a host array */, int on_device);
 /* the HIP device the plan lives on -- where a caller allocates what it hands over with on_device; -1 for a null plan */
 int stmmqr_plan_device_index(const stmmqr_plan *plan);
+
+/* H of the held factorization -- the Householder vectors as compressed sparse columns, their Tau and the row permutation HPinv --
+ * made ON THE DEVICE from the resident factors (keepH = 1): nothing is downloaded but the entries kept, and with on_device nothing at
+ * all.  The matrix is the m x nh one stmmqr_plan_export_r returns as nh, Hp, Hi, Hx, HTau (walk_packed with n1rows = 0): the slots
+ * (front ascending, k = 0 .. fn - 1) are walked; a pivotal slot has t = Stair[k], a dead one (t == 0) t = rm, a live one rm++ (at most
+ * fm), both h = rm; a non-pivotal slot h = min(h + 1, fm); the slot is a column of H iff t >= h and Tau[k] != 0.0.  A column holds the
+ * unit diagonal (row id of front row h - 1, 1.0) and then, for the front rows i = h .. t - 1 in that order, the entries of front column
+ * k with value != 0.0 (exact zeros are dropped, -0.0 included).  Row ids are the permuted ones stmmqr_plan_download gives (Hii after
+ * qr_hpinv); the rows of a column are in front-row order, NOT ascending.  HTau[q] = Tau of the q-th column.  HPinv[i] = the position
+ * of row i of the factorized matrix in that permuted order: scatter w[HPinv[i]] = x[i], apply H_0 .. H_{nh-1} in order, and w is Q'x in
+ * the row order stmmqr_plan_qmult method 0 returns.  No econ: it does not apply to H (nor does the host export apply it).
+ * Two calls: Hp == Hi == Hx == HTau == NULL counts -- only info is written, and HPinv if given; with all four, colcap >= nh and cap >=
+ * hnz it fills: Hp gets nh + 1 entries, Hi / Hx hnz, HTau nh.  A fill call does not depend on an earlier count call (it counts again).
+ * colcap < nh or cap < hnz: STMMQR_ERR_INVALID naming both numbers, info written, every array untouched, the plan stays usable.
+ * HPinv ([m]) is optional in either call.  on_device: Hp, Hi, Hx, HTau and HPinv are device pointers on stmmqr_plan_device_index(plan);
+ * else host arrays, whose device images live for the length of the call (16 bytes per entry kept, 16 per column, 8 per row), and only
+ * the entries kept cross the bus.  info is always a host array: info[0] = nh, info[1] = hnz, info[2] = the entries visited before the
+ * zero test (unit diagonals included), info[3] = m.  Complete on return (the plan's stream is synchronised).
+ * Deterministic: positions come from scans and from ranks within a wave's ballot, no atomics -- the same bits run after run, and the
+ * bits of stmmqr_plan_export_r.  Every offset is 64-bit; the counts of one slot are int.
+ * Memory, made at the first call and kept with the plan (a plan that never calls this allocates nothing for it): 20 bytes per entry
+ * of Rj (two int counts, an int column number and a 64-bit offset per slot).  With the level-wise scratch (STMMQR_RESIDENT_CACHE=0) the
+ * count walk and the fill walk each put the levels back into front form.
+ * Refusals (STMMQR_ERR_INVALID, the message says why, nothing is written, the plan stays usable): null plan or nothing factorized, a
+ * plan that keeps no Householder vectors (keepH = 0), info NULL, some but not all of Hp / Hi / Hx / HTau NULL, colcap < 0 or cap < 0,
+ * a plan that does not hold the whole tree.  Out of scope: compressed rows of H, the singleton rows of the SparseQR object. */
+int stmmqr_plan_h_sparse(stmmqr_plan *plan, stm_long *Hp, stm_long *Hi, double *Hx, double *HTau, stm_long *HPinv, stm_long colcap,
+                         stm_long cap, stm_long *info /* [4], always a host array */, int on_device);
 int stmmqr_sparselq(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
                     const stmmqr_relax *relax, int device, stmmqr_qr **out);
 

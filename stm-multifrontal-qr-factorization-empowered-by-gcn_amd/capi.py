@@ -658,6 +658,16 @@ class HipQR:
         device -- nothing crosses the bus.  Reads R only."""
         return _r_sparse(self._h, self.sym["m"], self.sym["n"], form, ncol, econ, device)
 
+    def h_sparse(self, device: bool = False) -> dict:
+        """H of the held factorization made on the device (stmmqr_plan_h_sparse; needs keepH = 1): the Householder vectors as compressed
+        columns Hp / Hi / Hx (unit diagonal stored first, exact zeros dropped, rows = the permuted row ids in front-row order), HTau and
+        the row permutation HPinv -- the Hp / Hi / Hx / HTau of export_r and the HPinv of download(), bit for bit.  w[HPinv[i]] = x[i],
+        then H_0 .. H_{nh-1} applied in order, gives qmult(0, x).  Returns {"Hp", "Hi", "Hx", "HTau", "HPinv", "shape": (m, nh),
+        "info"}, info = (nh, hnz, entries visited before the zero test, m): numpy arrays, or with device=True torch tensors written on
+        the plan's device -- nothing crosses the bus (info stays a numpy array).  No torch.sparse_csc_tensor is built: the rows of a
+        column are not ascending, which that format asks for."""
+        return _h_sparse(self._h, self.sym["m"], device)
+
     def condest(self, kind: int = 1, iters: int = 0, ncol=None, with_vector: bool = False) -> dict:
         """The condition of R over its live pivot columns -- of A(:, live) -- estimated on the device (stmmqr_plan_condest).  kind 1:
         the one-norm, exact |R_live|_1 times Hager / Higham's estimate of |R_live^-1|_1 (LAPACK's dtrcon convention); kind 2: the
@@ -1011,6 +1021,7 @@ lib.stmmqr_plan_export_r.argtypes = [C.c_void_p, C.POINTER(QrSymbolicC), C.c_lon
                                      C.POINTER(c_double_p)]
 lib.stmmqr_plan_r_sparse.argtypes = [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, c_long_p, C.c_int]
 lib.stmmqr_plan_device_index.argtypes = [C.c_void_p]
+lib.stmmqr_plan_h_sparse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_long, c_long_p, C.c_int]
 lib.stmmqr_sparselq.argtypes = [C.c_int, C.c_double, C.c_long, C.c_long, c_long_p, c_long_p, c_double_p, C.POINTER(Relax), C.c_int,
                                 C.POINTER(C.c_void_p)]
 lib.stmmqr_free.restype = None
@@ -1055,6 +1066,32 @@ def _r_sparse(plan, m, n, form, ncol, econ, device):
            "stmmqr_plan_r_sparse")
     make = torch.sparse_csc_tensor if code == 0 else torch.sparse_csr_tensor
     return make(tptr, tidx[:nnz], tval[:nnz], size=(m, ncol))
+
+
+def _h_sparse(plan, m, device):
+    """stmmqr_plan_h_sparse on a plan handle of a factorization with m rows: the count call, the arrays, the fill call.  device=False:
+    {"Hp", "Hi", "Hx", "HTau", "HPinv", "shape": (m, nh), "info"} as numpy arrays; device=True: the same keys as int64 / float64 torch
+    tensors that live on the plan's device and were written there (info stays a numpy array)."""
+    info = np.zeros(4, I64)
+    _check(lib.stmmqr_plan_h_sparse(plan, None, None, None, None, None, 0, 0, _ip(info), 0), "stmmqr_plan_h_sparse")
+    nh, hnz = int(info[0]), int(info[1])
+    if not device:
+        Hp, Hi, Hx = np.zeros(nh + 1, I64), np.zeros(max(hnz, 1), I64), np.zeros(max(hnz, 1))
+        HTau, HPinv = np.zeros(max(nh, 1)), np.zeros(max(m, 1), I64)
+        _check(lib.stmmqr_plan_h_sparse(plan, Hp.ctypes.data, Hi.ctypes.data, Hx.ctypes.data, HTau.ctypes.data, HPinv.ctypes.data, nh, hnz,
+                                        _ip(info), 0), "stmmqr_plan_h_sparse")
+        return {"Hp": Hp, "Hi": Hi[:hnz], "Hx": Hx[:hnz], "HTau": HTau[:nh], "HPinv": HPinv[:m], "shape": (m, nh), "info": info}
+    import torch
+    dev = torch.device("cuda", int(lib.stmmqr_plan_device_index(plan)))
+    tHp = torch.empty(nh + 1, dtype=torch.int64, device=dev)
+    tHi = torch.empty(max(hnz, 1), dtype=torch.int64, device=dev)
+    tHx = torch.empty(max(hnz, 1), dtype=torch.float64, device=dev)
+    tTau = torch.empty(max(nh, 1), dtype=torch.float64, device=dev)
+    tPinv = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    _check(lib.stmmqr_plan_h_sparse(plan, tHp.data_ptr(), tHi.data_ptr(), tHx.data_ptr(), tTau.data_ptr(), tPinv.data_ptr(), nh, hnz,
+                                    _ip(info), 1), "stmmqr_plan_h_sparse")
+    return {"Hp": tHp, "Hi": tHi[:hnz], "Hx": tHx[:hnz], "HTau": tTau[:nh], "HPinv": tPinv[:m], "shape": (m, nh), "info": info}
 
 
 def _symbolic_dict(S, m, n) -> dict:
@@ -1157,6 +1194,13 @@ class SparseQR:
         it), without the download -- and with device=True as a torch sparse tensor that never left the device."""
         S = lib.stmmqr_sparseqr_symbolic_view(self._h).contents
         return _r_sparse(lib.stmmqr_sparseqr_plan(self._h), int(S.m), int(S.n), form, ncol, econ, device)
+
+    def h_sparse(self, device: bool = False) -> dict:
+        """HipQR.h_sparse on the object's plan: H, HTau and HPinv of the multifrontal part, as export_r gives them (the singleton rows
+        are not part of it), without the download -- and with device=True as torch tensors that never left the device (no
+        torch.sparse_csc_tensor: the rows of a column of H are not ascending)."""
+        S = lib.stmmqr_sparseqr_symbolic_view(self._h).contents
+        return _h_sparse(lib.stmmqr_sparseqr_plan(self._h), int(S.m), device)
 
     @classmethod
     def lq(cls, m, n, Ap, Ai, Ax, tol=-2.0, relax: Relax | None = None, device=-1):

@@ -9,6 +9,7 @@
 //   stmmqr_pack.hip      k_cpack, k_rh_*, k_zero_slabs, k_panel_msg                              (qr_cpack, qr_rhpack)
 //   stmmqr_resident.hip  Q-apply / triangular solves on the resident factors
 //   stmmqr_rsparse.hip   R of the resident factors as compressed sparse columns / rows: count, scan, compact
+//   stmmqr_hsparse.hip   H of the resident factors as compressed sparse columns, HTau, HPinv: count, scan, compact (shared: stmmqr_rsdev.h)
 //   stmmqr_nullspace.hip null-space basis of R: Gram matrix, Cholesky factorization, the minimum-norm projector
 // (stmmqr_capanel.hip: the Gram-based panel.)  Kernels are compiled one by one, so the split changes no kernel's code.
 #pragma once

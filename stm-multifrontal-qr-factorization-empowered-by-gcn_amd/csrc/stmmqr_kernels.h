@@ -207,6 +207,17 @@ int stm_launch_rs_item_sums(const int *cp, const int *slot, const int *cnt, cons
                             hipStream_t st);
 int stm_launch_rs_scan(long long *ptr, long long nitems, const long long *part, int nparts, long long rtot, long long *info, hipStream_t st);
 int stm_launch_rs_slot_offsets(const int *cp, const int *slot, const int *cnt, const long long *ptr, long long *off, int ncol, hipStream_t st);
+// H as a sparse matrix in device memory (stmmqr_hsparse.hip), the level walk of the columns of R on the rows below them.  count writes
+// every slot's kept / visited entries and whether it is a column of H (cnt / vis / col: one int per slot of Rj each, the unit diagonal
+// counted); scan turns cnt into every slot's start (off) and col into its column number and writes info (4: nh, hnz, visited, m);
+// cols writes Hp (nh + 1) and HTau (nh) from them, fill writes Hi / Hx (row ids through Hii and wmap), pinv HPinv[i] = wmap[plinv[i]].
+int stm_launch_hs_count(const DevCtx &c, const int *flist, int nfr, int max_slab, int *cnt, int *vis, int *col, hipStream_t st);
+int stm_launch_hs_scan(const int *cnt, const int *vis, int *col, long long *off, long long nslots, long long m, long long *info, hipStream_t st);
+int stm_launch_hs_cols(const double *Tau, const int *cnt, const int *col, const long long *off, int nslots, const long long *info, long long *Hp,
+                       double *HTau, hipStream_t st);
+int stm_launch_hs_fill(const DevCtx &c, const int *flist, int nfr, int max_slab, const int *wmap, const long long *off, long long *Hi, double *Hx,
+                       hipStream_t st);
+int stm_launch_hs_pinv(const int *plinv, const int *wmap, int m, long long *HPinv, hipStream_t st);
 // null-space basis of R and the minimum-norm projector (stmmqr_nullspace.hip).  N is ncol x d (ld = ncol, R's column order), G = N'N
 // and its Cholesky factor L are d x d (ld = d): the blocks below the diagonal in place, the 32 x 32 diagonal blocks of L in Ld (1024
 // doubles each, the identity beyond d).  Every offset into N, G and the partial sums is 64-bit.

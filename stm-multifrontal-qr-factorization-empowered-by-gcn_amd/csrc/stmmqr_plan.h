@@ -11,7 +11,7 @@
 //   stmmqr_run.cpp       the step scheduler (stm_run_schedule: one step, serial, look-ahead, passengers), the pack pass
 //   stmmqr_multi.cpp     contribution blocks / panels in and out of a plan, shared fronts, the RCCL transport
 //   stmmqr_rfactor.cpp   Q-apply and triangular solves on the resident factors; with stmmqr_rcond.cpp (products with R,
-//                        condition estimate), stmmqr_rsparse.cpp (R out as a sparse matrix), stmmqr_rcov.cpp (selected inverse), stmmqr_seminormal.cpp (products with A, seminormal
+//                        condition estimate), stmmqr_rsparse.cpp / stmmqr_hsparse.cpp (R / H out as a sparse matrix), stmmqr_rcov.cpp (selected inverse), stmmqr_seminormal.cpp (products with A, seminormal
 //                        solves) and the pure stmmqr_restables.cpp: stmmqr_resident.h
 //   stmmqr_seam.cpp      the drop-in seam qr_factorize with the reference's structs, its plan cache
 #pragma once

@@ -1,8 +1,9 @@
 // stmmqr_resident.h -- the state of the operations on the resident factors (stmmqr_plan::res), sorted by how long it lives, and what
-// their six host units share (included by stmmqr_plan.h, after DevBuf):
+// their seven host units share (included by stmmqr_plan.h, after DevBuf):
 //   stmmqr_rfactor.cpp     the front form, the row map, the passes over the tree; qmult, rsolve, solve, solve_minnorm, solve_carried
 //   stmmqr_rcond.cpp       products with R and R', the condition estimate
 //   stmmqr_rsparse.cpp     R out as compressed columns / rows in device memory
+//   stmmqr_hsparse.cpp     H, HTau and HPinv out in device memory
 //   stmmqr_rnull.cpp       the null-space basis of R, its Gram matrix and Cholesky factor, the minimum-norm projector
 //   stmmqr_rcov.cpp        the selected inverse: variances, leverages, covariance entries
 //   stmmqr_seminormal.cpp  products with A, the seminormal solves, the minimum-norm forwarder of the SparseQR object
@@ -29,6 +30,10 @@ struct ResidentState {
         // entries (two ints) and its start (64-bit); per row of R the same two counts; a partial sum per 256 items, the four of info
         DevBuf<int> d_rsSlot, d_rsRow;
         DevBuf<long long> d_rsOff, d_rsPart, d_rsInfo;
+        // H as a sparse matrix (stmmqr_hsparse.cpp), made by the first call and kept: per slot of Rj its kept and visited entries and
+        // its column number in H (three ints) and its start (64-bit); the four of info
+        DevBuf<int> d_hsSlot;
+        DevBuf<long long> d_hsOff, d_hsInfo;
         // grouped split Q-apply (k_qbig_step4): allocated at the first Q-apply that wants it (t4_tried); t4_ok: there was room
         bool t4_ok = false, t4_tried = false;
         DevBuf<Qt4ItemHost> d_t4items;
@@ -107,6 +112,7 @@ int grow(DevBuf<double> &d, size_t n);
 int copy_cols(double *dst, long ldd, const double *src, long lds, long rows, long cols, hipMemcpyKind kind, hipStream_t st);
 int stage_in(DevBuf<double> &d, const double *src, long ld, long rows, long cols, int on_device, hipStream_t st);
 int stage_out(const DevBuf<double> &d, double *dst, long ld, long rows, long cols, int on_device, hipStream_t st);
+int to_host(void *dst, const void *src, size_t bytes, hipStream_t st);   // bytes from the device on the stream, not waited for (0 bytes: no call)
 // count longs as ints: t receives the host copy, which the upload reads until the caller's next synchronize (HIP's code: the caller words it)
 int upload_narrowed(DevBuf<int> &d, const long *v, size_t count, std::vector<int> &t, hipStream_t st);
 // the passes (stmmqr_rfactor.cpp says what they read and write)

@@ -79,6 +79,11 @@ int copy_cols(double *dst, long ldd, const double *src, long lds, long rows, lon
                                 kind, st));
     return 0;
 }
+int to_host(void *dst, const void *src, size_t bytes, hipStream_t st)
+{
+    if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+    return 0;
+}
 int grow(DevBuf<double> &d, size_t n) { return (d.p && d.n >= n) ? 0 : d.alloc(std::max<size_t>(n, 1)); }
 int stage_in(DevBuf<double> &d, const double *src, long ld, long rows, long cols, int on_device, hipStream_t st)
 {

@@ -22,11 +22,6 @@ int ensure_rsparse(stmmqr_plan &P, int form)
     } else if (!S.d_rsRow.p) LCHK(S.d_rsRow.alloc(2 * rows));
     return 0;
 }
-int to_host(void *dst, const void *src, size_t bytes, hipStream_t st)
-{
-    if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    return 0;
-}
 }  // namespace
 
 int stmmqr_plan_device_index(const stmmqr_plan *plan) { return plan ? plan->device : -1; }
