@@ -164,7 +164,7 @@ __device__ __forceinline__ void dev_subpanel_reg(PanelShared &ps, double *F, lon
 #pragma unroll
                 for (int x = 0; x < SWT; x++) ps.top[par][x] = a[0][x];
             }
-            const double rw = wave_reduce8(part);
+            const double rw = wave_reduce8<SWT>(part);  // (sum[SWT..7] below: unspecified, never read)
             if (lane < 8) ps.rsum[par][wid * 8 + lane] = rw;
             __syncthreads();
             const double rb = wave_sum_stride8((lane < NWV * 8) ? ps.rsum[par][lane] : 0.0);
@@ -601,12 +601,14 @@ __device__ __forceinline__ void publish_progress(int *flag, int value)
     if (threadIdx.x == 0) st_agent(flag, value);
 }
 
+// (nv: part[nv..7] are structurally zero -- wave_reduce8<NV>, nv being the index arithmetic of an unrolled loop; sum[nv..7] come
+//  back unspecified and no caller may read them)
 template <int NTH>
-__device__ __forceinline__ void block_reduce8(PanelShared &ps, int &par, const double (&part)[8], double (&sum)[8])
+__device__ __forceinline__ void block_reduce8(PanelShared &ps, int &par, const double (&part)[8], double (&sum)[8], int nv = 8)
 {
     constexpr int NWV = NTH / 64;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const double rw = wave_reduce8(part);
+    const double rw = wave_reduce8_n(part, nv);
     if (lane < 8) ps.rsum[par][wid * 8 + lane] = rw;
     lds_barrier();
     const double rb = wave_sum_stride8((lane < NWV * 8) ? ps.rsum[par][lane] : 0.0);
@@ -688,6 +690,8 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
     constexpr int NPART = (SWT == 8) ? STM_TALL_NPART : (SWT == 4) ? STM_TALL_NPART4 : 2;      // a group publishes its columns in this many parts
     constexpr int HW = SWT / NPART;                            // reflectors per published part
     constexpr int NPV = HW * SWT, NGP = (NPV + 7) / 8;         // V'C products, in exchange groups of eight
+    constexpr int NVP = NPV < 8 ? NPV : 8;                     // live products of every exchange group (wave_reduce8<NV>)
+    static_assert(NPV < 8 || NPV % 8 == 0, "the last exchange group of V'C would be partly padding");
     // (a group publishes in NPART parts -- after every HW of its columns -- so that the next group applies the earlier reflectors
     //  while the later ones are still being factorized)
     int seen = -1;
@@ -759,7 +763,7 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
                     gv[q1 * HW - (q1 * (q1 + 1)) / 2 + (q2 - q1 - 1)] = acc;
                 }
             }
-            const double rw = wave_reduce8(gv);
+            const double rw = wave_reduce8<HW * (HW - 1) / 2>(gv);   // (G8 is read below this count only)
             if (lane < 8) ps.rsumB[0][wid * 8 + lane] = rw;
         }
 #pragma unroll
@@ -775,7 +779,7 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
                 }
                 pv[e] = acc;
             }
-            const double rw = wave_reduce8(pv);
+            const double rw = wave_reduce8<NVP>(pv);           // (P8[e] is read for gi * 8 + e < NPV only)
             if (lane < 8) ps.rsumB[1 + gi][wid * 8 + lane] = rw;
         }
         lds_barrier();
@@ -931,7 +935,7 @@ __device__ __forceinline__ void dev_tall_group(PanelShared &ps, const FrontSym &
                 for (int x = j; x < SWT; x++) ps.top[tpar][x - j] = a[0][x];
             }
             TCY(1);
-            block_reduce8<NTH>(ps, par, part, sum);
+            block_reduce8<NTH>(ps, par, part, sum, SWT - j);   // (part[0 .. SWT-j-1] are live; sum[x] is read for x < SWT - j)
             TCY(2);
             const double alpha = ps.top[tpar][0];
             const double ss = sum[0];
@@ -1136,7 +1140,7 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
 #pragma unroll
                 for (int x = 0; x < SW; x++) pv[x] += v[r] * a[r][x];
             }
-            const double rw = wave_reduce8(pv);
+            const double rw = wave_reduce8<SW>(pv);
             double wv[SW];
             wv[0] = tau * lane_bcast<red8_lane(0)>(rw); wv[1] = tau * lane_bcast<red8_lane(1)>(rw);
             wv[2] = tau * lane_bcast<red8_lane(2)>(rw); wv[3] = tau * lane_bcast<red8_lane(3)>(rw);
@@ -1183,7 +1187,10 @@ __device__ __forceinline__ void dev_wave_panel(PanelShared &ps, WaveShared &wsh,
 #pragma unroll
                     for (int y = x; y < SW; y++) part[y - x] += xv * a[r][y];
                 }
-                const double rw = wave_reduce8(part);
+                // (SW - x live sums, and sum[y] is read for y < SW - x only.  With 4 columns per wave only the first column is
+                //  sized: SW - x in the other three costs k_panel_pc a spilled scalar more than the unsized form has, 429 against
+                //  428, and the compiler already folds most of their constant zeros)
+                const double rw = wave_reduce8_n(part, SW == 8 ? SW - x : (x == 0 ? SW : 8));
                 const double sum0 = lane_bcast<red8_lane(0)>(rw), sum1 = lane_bcast<red8_lane(1)>(rw);
                 const double sum2 = lane_bcast<red8_lane(2)>(rw), sum3 = lane_bcast<red8_lane(3)>(rw);
                 double sum[SW] = {sum0, sum1, sum2, sum3};

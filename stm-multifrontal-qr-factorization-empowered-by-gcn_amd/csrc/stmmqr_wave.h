@@ -69,30 +69,66 @@ __device__ __forceinline__ int wave_max_int(int v)
     return v;
 }
 
+//
+// NV sizes the butterfly to the sums a caller has: v[NV .. 7] are zero by the caller's CODE (padding, not data) and are never
+// read.  One exchange-add pairs a lower member (kept by the lanes on side 0) with an upper member (kept by side 1):
+//   both live        : keep = side ? up : lo, send = side ? lo : up, keep + moved(send)   -- 4 selects, 2 DPP moves, 1 add
+//   upper one zero   : lo + moved(lo) in EVERY lane                                       -- 2 DPP moves, 1 add
+//   both zero        : the pair does not exist
+// Side 0 of the middle form computes lo(l) + lo(partner), the expression the full form has there (its partner sends lo), so the
+// lanes l with red8_idx(l) < NV end with the bits of the unsized butterfly.  Side 1, where the full form has 0 + 0, holds a
+// value nobody may read: lanes with red8_idx(l) >= NV are UNSPECIFIED after wave_reduce8<NV>.  They never reach a specified
+// lane: the side of a lane in a pair is one of the bits 0-2 of its number, and every later partner (l ^ 1, l ^ 2, row_ror:8,
+// l ^ 16, l ^ 32) keeps the bit of an earlier pair.
+// Instructions of the butterfly for NV = 8 .. 1: 49, 45, 41, 37, 33, 26, 19, 9.
+template <int CTRL, bool HAVE_UP>
+__device__ __forceinline__ double red8_pair(bool side, double lo, double up)
+{
+    if constexpr (HAVE_UP) {
+        const double keep = side ? up : lo;
+        const double send = side ? lo : up;
+        return keep + dpp_mov<CTRL>(send);
+    } else
+        return dpp_add<CTRL>(lo);
+}
+template <int NV = 8>
 __device__ __forceinline__ double wave_reduce8_partial(const double (&v)[8])
 {
+    static_assert(NV >= 1 && NV <= 8, "one to eight live sums");
     const int lane = threadIdx.x & 63;
     const bool sA = (lane >> 2) & 1, sB = lane & 1, sC = (lane >> 1) & 1;
-    double n4[4], n2[2];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {                       // partner 7 - (l & 7): the other quad
-        const double keep = sA ? v[i + 4] : v[i];
-        const double send = sA ? v[i] : v[i + 4];
-        n4[i] = keep + dpp_mov<0x141>(send);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; i++) {                       // partner l ^ 1
-        const double keep = sB ? n4[i + 2] : n4[i];
-        const double send = sB ? n4[i] : n4[i + 2];
-        n2[i] = keep + dpp_mov<0xB1>(send);
-    }
-    const double keep = sC ? n2[1] : n2[0];             // partner l ^ 2
-    const double send = sC ? n2[0] : n2[1];
-    return keep + dpp_mov<0x4E>(send);
+    constexpr int N4 = NV < 4 ? NV : 4, N2 = NV < 2 ? NV : 2;      // live values after the first / second halving
+    double n4[4] = {0.0, 0.0, 0.0, 0.0}, n2[2] = {0.0, 0.0};       // (entries past N4 / N2 are never read)
+    // partner 7 - (l & 7): the other quad
+    if constexpr (N4 > 0) n4[0] = red8_pair<0x141, (4 < NV)>(sA, v[0], v[4]);
+    if constexpr (N4 > 1) n4[1] = red8_pair<0x141, (5 < NV)>(sA, v[1], v[5]);
+    if constexpr (N4 > 2) n4[2] = red8_pair<0x141, (6 < NV)>(sA, v[2], v[6]);
+    if constexpr (N4 > 3) n4[3] = red8_pair<0x141, (7 < NV)>(sA, v[3], v[7]);
+    // partner l ^ 1
+    if constexpr (N2 > 0) n2[0] = red8_pair<0xB1, (2 < N4)>(sB, n4[0], n4[2]);
+    if constexpr (N2 > 1) n2[1] = red8_pair<0xB1, (3 < N4)>(sB, n4[1], n4[3]);
+    // partner l ^ 2
+    return red8_pair<0x4E, (1 < N2)>(sC, n2[0], n2[1]);
 }
+template <int NV = 8>
 __device__ __forceinline__ double wave_reduce8(const double (&v)[8])
 {
-    return wave_sum_stride8(wave_reduce8_partial(v));
+    return wave_sum_stride8(wave_reduce8_partial<NV>(v));
+}
+// The same with the count as a VALUE, for the index of a fully unrolled loop (not a constant expression of the language, a
+// constant by the time the switch is simplified: one case is left in each copy of the loop body).
+__device__ __forceinline__ double wave_reduce8_n(const double (&v)[8], int nv)
+{
+    switch (nv) {
+    case 1: return wave_reduce8<1>(v);
+    case 2: return wave_reduce8<2>(v);
+    case 3: return wave_reduce8<3>(v);
+    case 4: return wave_reduce8<4>(v);
+    case 5: return wave_reduce8<5>(v);
+    case 6: return wave_reduce8<6>(v);
+    case 7: return wave_reduce8<7>(v);
+    default: return wave_reduce8<8>(v);
+    }
 }
 
 // A value that is the same in every lane although the compiler cannot prove it (loaded by every lane from one address,
