@@ -886,6 +886,58 @@ int stmmqr_ls_condest(stmmqr_ls *ls, int kind, int iters, double *out, double *v
 int stmmqr_ls_nullspace(stmmqr_ls *ls, stm_long *ndead, double *N, stm_long ldn, int on_device);
 int stmmqr_ls_project_minnorm(stmmqr_ls *ls, double *X, stm_long ldx, stm_long nrhs, int on_device, double *info);
 void stmmqr_ls_free(stmmqr_ls *ls);
+int stmmqr_ls_dims(const stmmqr_ls *ls, stm_long *dims /* [4]: m, n of A, nrhs, damped (0 / 1) */);   /* either kind of object */
+
+/* ---- The damped mode of the least-squares object: min_x |W (A x - b_j)|^2 + |D x|^2, W = diag(w), D = diag(D_jj) >= 0 -------------------
+ * (Levenberg-Marquardt and trust-region steps, ridge regression, regularization paths, iteratively reweighted fits: w and D change
+ * from solve to solve, the pattern does not.)  The object is the plain object of the (m + n) x n matrix [W A; D] with the right-hand
+ * sides [W B; 0]: the same bits as stmmqr_ls_create / stmmqr_ls_solve on that matrix in the same column order.
+ * stmmqr_ls_create_damped, once per pattern and nrhs: the columns of A ALONE are ordered exactly as stmmqr_ls_create orders them (the
+ * same orderings, refusals and Quser rule; Qfill[0 .. n-1] equals the plain object's for the same arguments), then stmmqr_analyze runs
+ * on the pattern of the (m + n) x (n + nrhs) matrix [A; I | dense columns]: column j holds A's entries in their given order and then
+ * the entry of row m + j; the nrhs trailing columns are dense over all m + n rows (the zero block below B is stored: n * nrhs
+ * doubles).  Otherwise as stmmqr_ls_create: no singleton removal, an R-only plan, device -2 = the host half only, STMMQR_LS_MAX_NRHS.
+ * With a device the object also keeps there: A's values as given here (anz doubles), A's row indices and column pointers as int
+ * (anz + n + 1; a pattern of 2^31 or more entries or columns is refused), D (n doubles) and, for tol <= -2, the n + 1 64-bit column
+ * pointers of [A; I].  On failure *out is NULL.
+ * stmmqr_ls_solve_damped, any number of times: builds the values of [W A; D | W B; 0] on the device -- entry p of A (row i) becomes
+ * w[i] * Ax[p], ONE multiplication --, factorizes with ntol = n and calls stmmqr_plan_solve_carried.  Nothing is analysed or planned
+ * again and no solve leaves state for the next: the values are built anew every time from A's unweighted values.
+ *   Ax           NULL: the values given at create; else anz values, a device pointer with ax_on_device
+ *   on_device    B, X, resid and dmp->w, d, D_out, dnorm are device pointers (all of them, or none); dmp itself is a host struct
+ *   B m x nrhs (ldb >= m), X n x nrhs (ldx >= n), resid [nrhs] or NULL: resid[j] = sqrt(|W (b_j - A x_j)|^2 + |D x_j|^2), the carried
+ *   residual of the augmented problem.  With dnorm[j] = |D x_j|_2 and |W b_j| a caller has the predicted reduction of a step.
+ *   D_jj = sqrt(lambda) * s_j.  s_j = d[j]; or, d NULL, 1 (scale 0) or |W A(:,j)|_2 clamped to [scale_min, scale_max] (scale 1; a zero
+ *   column gets scale_min).  D_out [n], A's column order.
+ *   tol <= -2 at create: 20 ((m + n) + n) eps max_j |[W A; D](:,j)|_2, the rule of stmmqr_ls_create on the augmented matrix, evaluated on
+ *   the device from the built values; its 8-byte copy back is the only host wait before the factorization (none for a given tol).
+ * Refusals of the solve (STMMQR_ERR_INVALID, the message names the cause, nothing was touched, the object stays usable): a plain object
+ * (and stmmqr_ls_solve refuses a damped one), dmp NULL, lambda negative or not finite, scale not 0 or 1, scale 1 with scale_min not
+ * in (0, scale_max], the host half only, B or X NULL or ldb < m or ldx < n.  NaN or Inf in w, d or Ax is not searched for: it ends as
+ * in the plain object.  (With scale 1 D_out does not show it: a NaN column norm is clamped like any other and comes out as scale_min,
+ * while the NaN stays in the built values and reaches the factorization.)  A solve that fails in the factorization leaves the object usable for the next solve.
+ * The other entry points on a damped object, after a solve: stmmqr_ls_covariance_diag gives diag((A'W^2 A + D^2)^-1) [n];
+ * stmmqr_ls_leverage writes m + n values (lev [m + n]): the first m are the diagonal of the ridge hat matrix W A (A'W^2 A + D^2)^-1 A'W,
+ * whose sum is the effective degrees of freedom, and all m + n sum to the number of live columns; stmmqr_ls_condest gives the
+ * condition of [W A; D]; stmmqr_ls_covariance_entries, _nullspace, _project_minnorm and the plan's R export work unchanged;
+ * stmmqr_ls_info keeps its 14 fields (device bytes include what the damped mode holds).
+ * stmmqr_ls_damped_info: info[0] = device ms of building the values in the last solve (the tolerance's norm included), info[1] = device
+ * bytes the object holds beyond the plain object of [A; I]. */
+typedef struct {
+    const double *w;        /* [m] row weights, NULL: all 1                                   */
+    const double *d;        /* [n] column scales s_j, NULL: chosen by `scale`                  */
+    double lambda;          /* D_jj = sqrt(lambda) * s_j ; lambda >= 0 and finite              */
+    int scale;              /* d == NULL: 0 -> s_j = 1 (Levenberg, ridge);
+                                          1 -> s_j = |W A(:,j)|_2 clamped to [scale_min, scale_max] (Marquardt) */
+    double scale_min, scale_max;
+    double *D_out;          /* [n] or NULL: receives the D_jj used, in A's column order        */
+    double *dnorm;          /* [nrhs] or NULL: |D x_j|_2                                       */
+} stmmqr_ls_damping;
+int stmmqr_ls_create_damped(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
+                            stm_long nrhs, const stm_long *Quser, const stmmqr_relax *relax, int device, stmmqr_ls **out);
+int stmmqr_ls_solve_damped(stmmqr_ls *ls, const double *Ax, int ax_on_device, const stmmqr_ls_damping *dmp, const double *B,
+                           stm_long ldb, double *X, stm_long ldx, double *resid, int on_device);
+int stmmqr_ls_damped_info(const stmmqr_ls *ls, double *info /* [2] */);
 
 void stmmqr_shutdown(void);                           /* optional end-of-use call for dlopen()ing hosts: device sync  */
 /* Device buffers for hosts without HIP bindings of their own (FFI callers of stmmqr_export_front_dev /

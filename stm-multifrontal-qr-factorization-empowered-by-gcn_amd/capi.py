@@ -1339,12 +1339,27 @@ lib.stmmqr_ls_free.restype = None
 lib.stmmqr_ls_free.argtypes = [C.c_void_p]
 
 
+class LsDamping(C.Structure):
+    """stmmqr_ls_damping (include/stmmqr_hip.h)"""
+    _fields_ = [("w", C.c_void_p), ("d", C.c_void_p), ("lam", C.c_double), ("scale", C.c_int), ("scale_min", C.c_double),
+                ("scale_max", C.c_double), ("D_out", C.c_void_p), ("dnorm", C.c_void_p)]
+
+
+lib.stmmqr_ls_create_damped.argtypes = lib.stmmqr_ls_create.argtypes
+lib.stmmqr_ls_solve_damped.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LsDamping), C.c_void_p, C.c_long, C.c_void_p, C.c_long,
+                                       C.c_void_p, C.c_int]
+lib.stmmqr_ls_dims.argtypes = [C.c_void_p, c_long_p]
+lib.stmmqr_ls_damped_info.argtypes = [C.c_void_p, c_double_p]
+
+
 class LeastSquares:
     """min |A x - b| for nrhs right-hand sides with the right-hand sides carried through the factorization (stmmqr_ls_*): the
     columns of A are ordered as SparseQR orders them, [A B] is analysed once and factorized with ntol = n at every solve, and
     x = E R11^-1 C comes from R alone -- Q is never stored (an R-only plan).  Column singletons are not removed in this mode.
     solve() may be called again with new values and a new B (a Gauss-Newton loop): nothing is analysed or planned again.
     symbolic_only=True stops after the host half (no GPU needed)."""
+
+    _create = "stmmqr_ls_create"
 
     def __init__(self, m, n, Ap, Ai, Ax, nrhs=1, ordering=7, tol=-2.0, relax: Relax | None = None, Quser=None, device=-1,
                  symbolic_only=False):
@@ -1355,9 +1370,9 @@ class LeastSquares:
             raise StmmqrError("LeastSquares: Quser must hold one entry per column of A")
         self.anz = int(Ap[-1])
         self._h = C.c_void_p()
-        _check(lib.stmmqr_ls_create(int(ordering), float(tol), self.m, self.n, _ip(Ap), _ip(Ai), _dp(Ax), self.nrhs, _ip(Q),
-                                    None if relax is None else C.byref(relax), -2 if symbolic_only else int(device), C.byref(self._h)),
-               "stmmqr_ls_create")
+        _check(getattr(lib, self._create)(int(ordering), float(tol), self.m, self.n, _ip(Ap), _ip(Ai), _dp(Ax), self.nrhs, _ip(Q),
+                                          None if relax is None else C.byref(relax), -2 if symbolic_only else int(device),
+                                          C.byref(self._h)), self._create)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1381,6 +1396,13 @@ class LeastSquares:
         p._keep, p._borrowed, p._h = {}, True, h
         p.sym = {k: int(getattr(S, k)) for k in ["m", "n", "anz", "nf", "maxfn", "rjsize", "hisize"]}
         return p
+
+    @property
+    def dims(self) -> dict:
+        """m and n of A, nrhs, and whether the object is a damped one (stmmqr_ls_dims)"""
+        v = np.zeros(4, I64)
+        _check(lib.stmmqr_ls_dims(self._h, _ip(v)), "stmmqr_ls_dims")
+        return {"m": int(v[0]), "n": int(v[1]), "nrhs": int(v[2]), "damped": bool(v[3])}
 
     @property
     def info(self) -> dict:
@@ -1487,6 +1509,80 @@ class LeastSquares:
         if dof <= 0:
             return np.full((self.n, self.nrhs), np.inf)
         return np.sqrt(var[:, None] * (resid[None, :] ** 2 / dof))
+
+
+class DampedLeastSquares(LeastSquares):
+    """min |W (A x - b)|^2 + |D x|^2 with W = diag(w) and D = diag(sqrt(lam) * s) (stmmqr_ls_create_damped / stmmqr_ls_solve_damped):
+    Levenberg-Marquardt and trust-region steps, ridge regression, reweighted fits.  The columns of A are ordered as LeastSquares orders
+    them, [A; I | B; 0] is analysed once, and every solve() builds the values of [W A; D | W B; 0] on the device and factorizes them:
+    w, D, A's values and B may all change from call to call, nothing is analysed or planned again.  The object is the LeastSquares of
+    that (m + n) x n matrix, so after a solve variances() is diag((A'W^2 A + D^2)^-1), leverages() has m + n entries (the first m: the
+    diagonal of the ridge hat matrix, their sum the effective degrees of freedom) and condest() is the condition of [W A; D]."""
+
+    _create = "stmmqr_ls_create_damped"
+
+    def _damping(self, w, d, lam, scale, scale_min, scale_max, D_out, dnorm):
+        return LsDamping(w, d, float(lam), int(scale), float(scale_min), float(scale_max), D_out, dnorm)
+
+    @property
+    def damped_info(self) -> dict:
+        v = np.zeros(2)
+        _check(lib.stmmqr_ls_damped_info(self._h, _dp(v)), "stmmqr_ls_damped_info")
+        return {"ms_build": float(v[0]), "damped_bytes": float(v[1])}
+
+    def solve(self, B, Ax=None, w=None, d=None, lam=0.0, scale=0, scale_min=1e-6, scale_max=1e32):
+        """-> (X, resid, dnorm, D): X n x nrhs (a vector for a vector B), resid[j] = sqrt(|W (b_j - A x_j)|^2 + |D x_j|^2),
+        dnorm[j] = |D x_j|, D [n] the diagonal used.  Ax: new values of A (same pattern); w [m] row weights; d [n] column scales s_j, or
+        scale = 0 (s_j = 1) / 1 (s_j = |W A(:,j)| clamped to [scale_min, scale_max]); D_jj = sqrt(lam) * s_j."""
+        Bf = np.array(B, dtype=np.float64, order="F", copy=True).reshape(self.m, -1, order="F")
+        if Bf.shape[1] != self.nrhs:
+            raise StmmqrError(f"DampedLeastSquares.solve: B has {Bf.shape[1]} columns, the object was created for {self.nrhs}")
+        keep = {}
+        for name, a, size in (("Ax", Ax, self.anz), ("w", w, self.m), ("d", d, self.n)):
+            if a is not None:
+                keep[name] = np.ascontiguousarray(a, np.float64).reshape(-1)
+                if keep[name].size != size:
+                    raise StmmqrError(f"DampedLeastSquares.solve: {name} must hold {size} values")
+        ptr = lambda k: keep[k].ctypes.data if k in keep else None                                           # noqa: E731
+        X = np.zeros((max(self.n, 1), self.nrhs), order="F")
+        resid, dnorm, D = np.zeros(self.nrhs), np.zeros(self.nrhs), np.zeros(max(self.n, 1))
+        dmp = self._damping(ptr("w"), ptr("d"), lam, scale, scale_min, scale_max, D.ctypes.data, dnorm.ctypes.data)
+        _check(lib.stmmqr_ls_solve_damped(self._h, ptr("Ax"), 0, C.byref(dmp), Bf.ctypes.data, max(self.m, 1), X.ctypes.data, max(self.n, 1),
+                                          resid.ctypes.data, 0), "stmmqr_ls_solve_damped")
+        X = X[:self.n]
+        return (X[:, 0] if np.ndim(B) == 1 else X), resid, dnorm, D[:self.n]
+
+    def solve_dev(self, b_ptr: int, x_ptr: int, ax_ptr=None, w_ptr=None, d_ptr=None, lam=0.0, scale=0, scale_min=1e-6, scale_max=1e32,
+                  resid_ptr=None, dnorm_ptr=None, D_ptr=None):
+        """device pointers for every array: B (m x nrhs, ld m), X (n x nrhs, ld n), optionally A's values, w [m], d [n], and where
+        resid [nrhs], dnorm [nrhs] and D [n] go.  Returns the residual norms as a numpy array (stmmqr_ls_resid)."""
+        vp = lambda p: None if p is None else C.c_void_p(int(p))                                             # noqa: E731
+        dmp = self._damping(vp(w_ptr), vp(d_ptr), lam, scale, scale_min, scale_max, vp(D_ptr), vp(dnorm_ptr))
+        _check(lib.stmmqr_ls_solve_damped(self._h, vp(ax_ptr), 1, C.byref(dmp), vp(b_ptr), max(self.m, 1), vp(x_ptr), max(self.n, 1),
+                                          vp(resid_ptr), 1), "stmmqr_ls_solve_damped")
+        out = np.zeros(self.nrhs)
+        _check(lib.stmmqr_ls_resid(self._h, _dp(out)), "stmmqr_ls_resid")
+        return out
+
+    def diagnostics(self):
+        """after solve(): (leverages [m + n], variances [n]) from ONE selected inversion (stmmqr_ls_leverage)"""
+        lev, var = np.zeros(max(self.m + self.n, 1)), np.zeros(max(self.n, 1))
+        _check(lib.stmmqr_ls_leverage(self._h, lev.ctypes.data, var.ctypes.data, 0), "stmmqr_ls_leverage")
+        return lev[:self.m + self.n], var[:self.n]
+
+    def leverages(self, dev_ptr=None):
+        """after solve(): the m + n leverages of the rows of [W A; D].  The first m are the diagonal of the ridge hat matrix
+        W A (A'W^2 A + D^2)^-1 A'W, whose sum is the effective degrees of freedom; all m + n sum to the number of live columns.
+        dev_ptr: a device pointer that receives the m + n doubles (returns None)."""
+        if dev_ptr is not None:
+            _check(lib.stmmqr_ls_leverage(self._h, C.c_void_p(int(dev_ptr)), None, 1), "stmmqr_ls_leverage")
+            return None
+        lev = np.zeros(max(self.m + self.n, 1))
+        _check(lib.stmmqr_ls_leverage(self._h, lev.ctypes.data, None, 0), "stmmqr_ls_leverage")
+        return lev[:self.m + self.n]
+
+    def std_errors(self):
+        raise StmmqrError("DampedLeastSquares.std_errors: not defined for a damped fit (use variances() and the residuals)")
 
 
 def read_matrix_market(path):

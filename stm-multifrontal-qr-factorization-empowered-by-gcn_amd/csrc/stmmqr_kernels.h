@@ -240,6 +240,19 @@ int stm_launch_null_nt(const double *N, int ncol, int d, int slab, int nslab, co
 int stm_launch_null_llt(const double *L, const double *Ld, int d, double *T, int nb, hipStream_t st);
 int stm_launch_null_sub(const double *N, int ncol, int d, const double *T, int nb, double *X, long long ldx, hipStream_t st);
 int stm_launch_null_norm2(const double *A, long long lda, int n, int nb, double *out, hipStream_t st);
+// the values of [W A; D | W B; 0] of the damped least-squares object and |D x_j|_2 (stmmqr_lsbuild.hip).  ap / ai: A's column pointers
+// and row indices as int; val: the augmented values (entry p of column j at p + j, D_jj at ap[j + 1] + j, then the B block of
+// (m + n) x nrhs); D [n].  values: w NULL = all 1.  diag: D_jj = sl * d[j] (d NULL: sl; d may be D).  marquardt: D_jj = sl * the clamped
+// 2-norm of the built column j.  rhs: in place on the B block, whose rows 0 .. m-1 hold B.  dnorm: out[k] = |D x_k|_2, X n x nrhs.
+int stm_launch_lsb_values(long long anz, int n, const int *ap, const int *ai, const double *Ax, const double *w, double *val, hipStream_t st);
+int stm_launch_lsb_diag(int n, const int *ap, const double *d, double sl, double *D, double *val, hipStream_t st);
+int stm_launch_lsb_marquardt(int n, const int *ap, double sl, double smin, double smax, double *D, double *val, hipStream_t st);
+int stm_launch_lsb_rhs(long long m, long long n, int nrhs, const double *w, double *Bv, hipStream_t st);
+int stm_launch_lsb_dnorm(int n, int nrhs, const double *D, const double *X, long long ldx, double *out, hipStream_t st);
+// k_rf_colnorm (stmmqr_refactor.hip): the largest column 2-norm of the ncol columns ap (64-bit pointers) of Ax, bit for bit the one
+// stm_qr_default_tol takes, as the bits of a non-negative double combined into *mx_bits by an atomic maximum (mx_bits leads a block of
+// 16 bytes -- the refactorization's head -- which the caller zeroes first); tsrc: NULL, or the storage position of every entry
+int stm_launch_rf_colnorm(long long ncol, const long long *ap, const int *tsrc, const double *Ax, unsigned long long *mx_bits, hipStream_t st);
 int stm_launch_panel_msg(void *const homes[6], const long long offs[6], const long long bytes[6], void *buf, int out, hipStream_t st);
 // subtree exchange: contribution blocks between plans as fixed-size messages, packed / unpacked on the device (stmmqr_pack.hip)
 struct StmFrontMsg { long long off, slot; int f, pad; };      // front f at buf + off: [8 | slot | fn - fp] doubles

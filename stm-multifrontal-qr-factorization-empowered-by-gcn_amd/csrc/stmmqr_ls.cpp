@@ -2,11 +2,17 @@
 // create (once per pattern and nrhs): the column order stmmqr_sparseqr gives A, the B columns appended unpermuted, stmmqr_analyze of
 // the pattern [A | nrhs dense columns], an R-only plan.  solve (any number of times, new values and new B: a Gauss-Newton loop):
 // the values [Ax | B] put together on the device, the factorization with ntol = n, stmmqr_plan_solve_carried.  Q is never stored.
+// The damped mode (stmmqr_ls_create_damped / stmmqr_ls_solve_damped): min |W (A x - b)|^2 + |D x|^2 as the plain object of the
+// (m + n) x n matrix [W A; D] with the right-hand sides [W B; 0].  A's columns are ordered as the plain object orders them, the
+// analysis is made once of the pattern [A; I | dense columns], and every solve builds the values on the device from
+// (Ax, w, d, lambda, B) with the kernels of stmmqr_lsbuild.hip: no host round trip, nothing analysed or planned again.
 #include <cfloat>
+#include <climits>
 #include <memory>
 #include <new>
 
 #include "stmmqr_plan.h"
+#include "stmmqr_sparseqr.h"          // (stm_qr_tol_of_maxnorm)
 
 struct stmmqr_ls {
     stm_long m = 0, n = 0, nrhs = 0, anz = 0;
@@ -25,9 +31,26 @@ struct stmmqr_ls {
     stmmqr_stats stats = {};
     double sym_info[8] = {}, solve_ms = 0;
     stm_long rank1 = 0, nanalyses = 0, nplans = 0, nsolves = 0;
+    // ---- the damped mode: m, anz, Ap, Bp, Bi above are those of [A; I] (m = rows of A + n, anz = entries of A + n), Ax holds A's own
+    // values as at create, and ax_current says that d_ax (not d_val, which every solve builds anew) holds them
+    bool damped = false;
+    stm_long am = 0, aanz = 0;                          // rows and entries of A
+    DevBuf<int> d_ap, d_ai;                             // A's column pointers and row indices, uploaded once at create
+    DevBuf<long long> d_ap2;                            // the column pointers of [A; I] for k_rf_colnorm (default tolerance only)
+    DevBuf<double> d_ax;                                // A's unweighted values: those of create, or a host array given to a solve
+    DevBuf<double> d_D;                                 // [n] the D_jj of the last solve, A's column order
+    DevBuf<double> d_head;                              // two doubles: where k_rf_colnorm leaves the largest column norm
+    DevBuf<double> d_w, d_x, d_dn;                      // for host arrays (made when first needed): w, X; |D x_j| of the last solve
+    hipEvent_t ev_build[2] = {nullptr, nullptr};
+    double build_ms = 0;
+    double damped_bytes() const
+    {
+        return 4.0 * (double)(d_ap.n + d_ai.n) + 8.0 * (double)(d_ap2.n + d_ax.n + d_D.n + d_head.n + d_w.n + d_x.n + d_dn.n);
+    }
     ~stmmqr_ls()
     {
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : ev_build) if (e) (void)hipEventDestroy(e);
         if (plan) stmmqr_plan_destroy(plan);
         if (sym) stmmqr_analysis_free(sym);
     }
@@ -35,24 +58,32 @@ struct stmmqr_ls {
 
 extern "C" {
 
-static int ls_create_impl(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
-                          stm_long nrhs, const stm_long *Quser, const stmmqr_relax *relax, int device, stmmqr_ls **out)
+// the refusals both kinds of object share at create (what = the entry point's name); *out = NULL
+static int ls_create_args(const std::string &what, int ordering, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai,
+                          const double *Ax, stm_long nrhs, const stm_long *Quser, stmmqr_ls **out)
 {
-    if (!out) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_create: null output");
+    if (!out) return fail(STMMQR_ERR_INVALID, what + ": null output");
     *out = nullptr;
-    if (m < 0 || n < 0 || !Ap || (Ap[n] > 0 && (!Ai || !Ax))) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_create: bad matrix");
-    if (nrhs < 1) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_create: nrhs must be at least 1");
+    if (m < 0 || n < 0 || !Ap || (Ap[n] > 0 && (!Ai || !Ax))) return fail(STMMQR_ERR_INVALID, what + ": bad matrix");
+    if (nrhs < 1) return fail(STMMQR_ERR_INVALID, what + ": nrhs must be at least 1");
     if (nrhs > STMMQR_LS_MAX_NRHS)
-        return fail(STMMQR_ERR_INVALID, "stmmqr_ls_create: nrhs = " + std::to_string(nrhs) + " exceeds the limit of " +
+        return fail(STMMQR_ERR_INVALID, what + ": nrhs = " + std::to_string(nrhs) + " exceeds the limit of " +
                                             std::to_string(STMMQR_LS_MAX_NRHS) + " right-hand sides per object");
     if (Quser && ordering == 3) {
         std::vector<char> seen((size_t)std::max<stm_long>(n, 1), 0);
         for (stm_long k = 0; k < n; k++) {
             if (Quser[k] < 0 || Quser[k] >= n || seen[(size_t)Quser[k]])
-                return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_create: Quser is not a permutation of the columns of A");
+                return fail(STMMQR_ERR_INVALID, what + ": Quser is not a permutation of the columns of A");
             seen[(size_t)Quser[k]] = 1;
         }
     }
+    return 0;
+}
+
+static int ls_create_impl(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
+                          stm_long nrhs, const stm_long *Quser, const stmmqr_relax *relax, int device, stmmqr_ls **out)
+{
+    PASS(ls_create_args("stmmqr_ls_create", ordering, m, n, Ap, Ai, Ax, nrhs, Quser, out));
     std::unique_ptr<stmmqr_ls> L(new stmmqr_ls());
     L->m = m; L->n = n; L->nrhs = nrhs; L->anz = Ap[n]; L->tol_arg = tol; L->device = device;
     L->Ap.assign(Ap, Ap + n + 1);
@@ -112,10 +143,78 @@ int stmmqr_ls_create(int ordering, double tol, stm_long m, stm_long n, const stm
     }
 }
 
+// The damped object: A's columns ordered as ls_create_impl orders them, then the plain object of the pattern [A; I] with that order
+// GIVEN; what the device path reads of A besides the plan goes up once.
+static int ls_create_damped_impl(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
+                                 stm_long nrhs, const stm_long *Quser, const stmmqr_relax *relax, int device, stmmqr_ls **out)
+{
+    PASS(ls_create_args("stmmqr_ls_create_damped", ordering, m, n, Ap, Ai, Ax, nrhs, Quser, out));
+    const stm_long anz = Ap[n];
+    if (device != -2 && (n >= INT_MAX || anz >= INT_MAX))
+        return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_create_damped: 2^31 or more columns or entries (the device tables of A are int)");
+    std::vector<stm_long> Q((size_t)std::max<stm_long>(n, 1), 0);
+    PASS(stm_sparseqr_order(ordering, tol, m, n, Ap, Ai, Ax, Quser, Q.data()));
+    // ---- [A; I]: column j = A's entries in their given order, then row m + j (the value 1 stands in until a solve builds D) ----
+    std::vector<stm_long> Cp((size_t)n + 1, 0), Ci((size_t)std::max<stm_long>(anz + n, 1), 0);
+    std::vector<double> Cx((size_t)std::max<stm_long>(anz + n, 1), 1.0);
+    for (stm_long j = 0; j < n; j++) {
+        Cp[(size_t)j] = Ap[j] + j;
+        for (stm_long p = Ap[j]; p < Ap[j + 1]; p++) {
+            if (Ai[p] < 0 || Ai[p] >= m) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_create_damped: row index out of range");
+            Ci[(size_t)(p + j)] = Ai[p]; Cx[(size_t)(p + j)] = Ax[p];
+        }
+        Ci[(size_t)(Ap[j + 1] + j)] = m + j;
+    }
+    Cp[(size_t)n] = anz + n;
+    stmmqr_ls *made = nullptr;
+    PASS(ls_create_impl(3, tol, m + n, n, Cp.data(), Ci.data(), Cx.data(), nrhs, n > 0 ? Q.data() : nullptr, relax, device, &made));
+    std::unique_ptr<stmmqr_ls> L(made);
+    L->damped = true; L->am = m; L->aanz = anz;
+    L->Ax.assign(Ax, Ax + anz);
+    if (L->plan) {
+        HIPCHK(hipSetDevice(L->plan->device));
+        HIPCHK(hipEventCreate(&L->ev_build[0]));
+        HIPCHK(hipEventCreate(&L->ev_build[1]));
+        std::vector<int> ap((size_t)n + 1), ai((size_t)std::max<stm_long>(anz, 1), 0);
+        for (stm_long j = 0; j <= n; j++) ap[(size_t)j] = (int)Ap[j];
+        for (stm_long p = 0; p < anz; p++) ai[(size_t)p] = (int)Ai[p];
+        LCHK(L->d_ap.alloc(ap.size()));
+        LCHK(L->d_ai.alloc((size_t)anz));
+        LCHK(L->d_ax.alloc((size_t)anz));
+        LCHK(L->d_D.alloc((size_t)n));
+        HIPCHK(hipMemcpy(L->d_ap.p, ap.data(), ap.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (anz > 0) {
+            HIPCHK(hipMemcpy(L->d_ai.p, ai.data(), (size_t)anz * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(L->d_ax.p, Ax, (size_t)anz * sizeof(double), hipMemcpyHostToDevice));
+        }
+        L->ax_current = true;
+        if (tol <= -2) {
+            std::vector<long long> ap2(Cp.begin(), Cp.end());
+            LCHK(L->d_ap2.alloc(ap2.size()));
+            LCHK(L->d_head.alloc(2));
+            HIPCHK(hipMemcpy(L->d_ap2.p, ap2.data(), ap2.size() * sizeof(long long), hipMemcpyHostToDevice));
+        }
+    }
+    *out = L.release();
+    return 0;
+}
+
+int stmmqr_ls_create_damped(int ordering, double tol, stm_long m, stm_long n, const stm_long *Ap, const stm_long *Ai, const double *Ax,
+                            stm_long nrhs, const stm_long *Quser, const stmmqr_relax *relax, int device, stmmqr_ls **out)
+{
+    try {
+        return ls_create_damped_impl(ordering, tol, m, n, Ap, Ai, Ax, nrhs, Quser, relax, device, out);
+    } catch (const std::bad_alloc &) {
+        if (out) *out = nullptr;
+        return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_ls_create_damped: out of memory");
+    }
+}
+
 int stmmqr_ls_solve(stmmqr_ls *ls, const double *Ax, int ax_on_device, const double *B, stm_long ldb, double *X, stm_long ldx,
                     double *resid, int on_device)
 {
     if (!ls) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve: null object");
+    if (ls->damped) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve: a damped object (stmmqr_ls_create_damped): use stmmqr_ls_solve_damped");
     if (!ls->plan) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve: the object holds the host half only (device = -2 at create)");
     stmmqr_ls &L = *ls;
     const stm_long m = L.m, n = L.n, k = L.nrhs, anz = L.anz;
@@ -177,6 +276,135 @@ int stmmqr_ls_solve(stmmqr_ls *ls, const double *Ax, int ax_on_device, const dou
     return 0;
 }
 
+// One damped solve: the values of [W A; D | W B; 0] built on the plan's stream, the factorization with ntol = n, the carried solve,
+// |D x_j|.  The only host wait before the factorization is the copy of the largest column norm (default tolerance).
+static int ls_solve_damped_impl(stmmqr_ls *ls, const double *Ax, int ax_on_device, const stmmqr_ls_damping *dmp, const double *B,
+                                stm_long ldb, double *X, stm_long ldx, double *resid, int on_device)
+{
+    if (!ls) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve_damped: null object");
+    if (!ls->damped) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve_damped: a plain object (stmmqr_ls_create): use stmmqr_ls_solve");
+    if (!dmp) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve_damped: null damping (dmp)");
+    if (!(dmp->lambda >= 0) || !std::isfinite(dmp->lambda))
+        return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve_damped: lambda must be finite and not negative");
+    if (dmp->scale != 0 && dmp->scale != 1) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve_damped: scale must be 0 or 1");
+    if (dmp->scale == 1 && !(dmp->scale_min > 0 && dmp->scale_min <= dmp->scale_max))
+        return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve_damped: scale = 1 needs 0 < scale_min <= scale_max");
+    if (!ls->plan)
+        return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve_damped: the object holds the host half only (device = -2 at create)");
+    stmmqr_ls &L = *ls;
+    const stm_long am = L.am, mn = L.m, n = L.n, k = L.nrhs, aanz = L.aanz, anz = L.anz;
+    if (!B || !X || ldb < am || ldx < n) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_solve_damped: bad arguments");
+    stmmqr_plan &P = *L.plan;
+    HIPCHK(hipSetDevice(P.device));
+    hipStream_t st = P.stream;
+    const hipMemcpyKind in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind back = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const double sl = std::sqrt(dmp->lambda);
+    // ---- the inputs on the device ----
+    const double *dAx = L.d_ax.p;
+    if (Ax && ax_on_device) dAx = Ax;
+    else if (Ax) {
+        L.ax_current = false;
+        if (aanz > 0) HIPCHK(hipMemcpyAsync(L.d_ax.p, Ax, (size_t)aanz * sizeof(double), hipMemcpyHostToDevice, st));
+    } else if (!L.ax_current) {
+        if (aanz > 0) HIPCHK(hipMemcpyAsync(L.d_ax.p, L.Ax.data(), (size_t)aanz * sizeof(double), hipMemcpyHostToDevice, st));
+        L.ax_current = true;
+    }
+    const double *dw = dmp->w;
+    if (dmp->w && !on_device) {
+        if (!L.d_w.p) LCHK(L.d_w.alloc((size_t)am));
+        if (am > 0) HIPCHK(hipMemcpyAsync(L.d_w.p, dmp->w, (size_t)am * sizeof(double), hipMemcpyHostToDevice, st));
+        dw = L.d_w.p;
+    }
+    const double *dd = dmp->d;
+    if (dmp->d && !on_device) {                             // (the scales go into D, which k_lsb_diag then rewrites in place)
+        if (n > 0) HIPCHK(hipMemcpyAsync(L.d_D.p, dmp->d, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+        dd = L.d_D.p;
+    }
+    double *dBv = L.d_val.p + anz;
+    if (am > 0)
+        HIPCHK(hipMemcpy2DAsync(dBv, (size_t)mn * sizeof(double), B, (size_t)ldb * sizeof(double), (size_t)am * sizeof(double), (size_t)k, in, st));
+    // ---- the values of [W A; D | W B; 0] ----
+    HIPCHK(hipEventRecord(L.ev_build[0], st));
+    HIPCHK((hipError_t)stm_launch_lsb_values((long long)aanz, (int)n, L.d_ap.p, L.d_ai.p, dAx, dw, L.d_val.p, st));
+    if (dd || dmp->scale == 0) HIPCHK((hipError_t)stm_launch_lsb_diag((int)n, L.d_ap.p, dd, sl, L.d_D.p, L.d_val.p, st));
+    else HIPCHK((hipError_t)stm_launch_lsb_marquardt((int)n, L.d_ap.p, sl, dmp->scale_min, dmp->scale_max, L.d_D.p, L.d_val.p, st));
+    HIPCHK((hipError_t)stm_launch_lsb_rhs((long long)am, (long long)n, (int)k, dw, dBv, st));
+    if (L.tol_arg <= -2) {                                  // the project's rule on [W A; D], from the built values
+        HIPCHK(hipMemsetAsync(L.d_head.p, 0, 2 * sizeof(double), st));
+        HIPCHK((hipError_t)stm_launch_rf_colnorm((long long)n, L.d_ap2.p, nullptr, L.d_val.p, (unsigned long long *)L.d_head.p, st));
+    }
+    HIPCHK(hipEventRecord(L.ev_build[1], st));
+    if (L.tol_arg <= -2) {
+        double mx = 0;
+        HIPCHK(hipMemcpyAsync(&mx, L.d_head.p, sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        L.tol = stm_qr_tol_of_maxnorm(mn, n, mx);
+    }
+    // ---- factorize, the B columns never rank-tested; solve with R alone ----
+    const bool first = !L.pattern_given;
+    PASS(stmmqr_factorize_device(L.plan, first ? L.Bp.data() : nullptr, first ? L.Bi.data() : nullptr, L.d_val.p, 1, L.tol, n, &L.stats));
+    L.pattern_given = true;
+    HIPCHK(hipEventRecord(L.ev[0], st));
+    double *dX = X;
+    stm_long ldd = ldx;
+    if (!on_device) {
+        ldd = std::max<stm_long>(n, 1);
+        if (!L.d_x.p) LCHK(L.d_x.alloc((size_t)(ldd * k)));
+        dX = L.d_x.p;
+    }
+    if (!L.d_resid.p) LCHK(L.d_resid.alloc((size_t)k));
+    if (!L.d_dn.p) LCHK(L.d_dn.alloc((size_t)k));
+    L.resid.assign((size_t)k, 0.0);
+    PASS(stmmqr_plan_solve_carried(L.plan, k, dX, ldd, L.d_resid.p, 1));
+    HIPCHK((hipError_t)stm_launch_lsb_dnorm((int)n, (int)k, L.d_D.p, dX, (long long)ldd, L.d_dn.p, st));
+    HIPCHK(hipMemcpyAsync(L.resid.data(), L.d_resid.p, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (resid) HIPCHK(hipMemcpyAsync(resid, L.d_resid.p, (size_t)k * sizeof(double), back, st));
+    if (dmp->dnorm) HIPCHK(hipMemcpyAsync(dmp->dnorm, L.d_dn.p, (size_t)k * sizeof(double), back, st));
+    if (dmp->D_out && n > 0) HIPCHK(hipMemcpyAsync(dmp->D_out, L.d_D.p, (size_t)n * sizeof(double), back, st));
+    if (!on_device && n > 0)
+        HIPCHK(hipMemcpy2DAsync(X, (size_t)ldx * sizeof(double), dX, (size_t)ldd * sizeof(double), (size_t)n * sizeof(double), (size_t)k,
+                                hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(L.ev[1], st));
+    std::vector<char> rd((size_t)std::max<stm_long>(n, 1), 0);
+    if (n > 0) HIPCHK(hipMemcpyAsync(rd.data(), P.d_Rdead.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, L.ev[0], L.ev[1]));
+    L.solve_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, L.ev_build[0], L.ev_build[1]));
+    L.build_ms = ms;
+    L.rank1 = 0;
+    for (stm_long j = 0; j < n; j++) L.rank1 += !rd[(size_t)j];
+    L.nsolves++;
+    return 0;
+}
+
+int stmmqr_ls_solve_damped(stmmqr_ls *ls, const double *Ax, int ax_on_device, const stmmqr_ls_damping *dmp, const double *B, stm_long ldb,
+                           double *X, stm_long ldx, double *resid, int on_device)
+{
+    try {
+        return ls_solve_damped_impl(ls, Ax, ax_on_device, dmp, B, ldb, X, ldx, resid, on_device);
+    } catch (const std::bad_alloc &) {
+        return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_ls_solve_damped: out of memory");
+    }
+}
+
+int stmmqr_ls_dims(const stmmqr_ls *ls, stm_long *dims)
+{
+    if (!ls || !dims) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_dims: null argument");
+    dims[0] = ls->damped ? ls->am : ls->m; dims[1] = ls->n; dims[2] = ls->nrhs; dims[3] = ls->damped ? 1 : 0;
+    return 0;
+}
+
+int stmmqr_ls_damped_info(const stmmqr_ls *ls, double *info)
+{
+    if (!ls || !info) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_damped_info: null argument");
+    if (!ls->damped) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_damped_info: a plain object (stmmqr_ls_create)");
+    info[0] = ls->build_ms; info[1] = ls->damped_bytes();
+    return 0;
+}
+
 const stm_qr_symbolic *stmmqr_ls_symbolic_view(const stmmqr_ls *ls) { return (ls && ls->sym) ? stmmqr_analysis_symbolic(ls->sym) : nullptr; }
 stmmqr_plan *stmmqr_ls_plan(stmmqr_ls *ls) { return ls ? ls->plan : nullptr; }
 
@@ -185,7 +413,7 @@ int stmmqr_ls_info(const stmmqr_ls *ls, double *info)
     if (!ls || !info) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_info: null argument");
     const stm_qr_symbolic *S = stmmqr_analysis_symbolic(ls->sym);
     info[0] = (double)ls->rank1; info[1] = (double)S->nf; info[2] = ls->stats.flops; info[3] = ls->sym_info[0];
-    info[4] = ls->stats.ms_total; info[5] = ls->solve_ms; info[6] = ls->stats.device_bytes + (double)ls->d_val.n * sizeof(double);
+    info[4] = ls->stats.ms_total; info[5] = ls->solve_ms; info[6] = ls->stats.device_bytes + (double)ls->d_val.n * sizeof(double) + ls->damped_bytes();
     info[7] = (double)ls->stats.retries; info[8] = (double)ls->stats.reschedules;
     info[9] = (double)ls->nanalyses; info[10] = (double)ls->nplans; info[11] = (double)ls->nsolves;
     info[12] = ls->tol; info[13] = (double)ls->nrhs;

@@ -170,9 +170,7 @@ int refactorize(stmmqr_qr *qr, const double *Ax, int ax_on_device)
     HIPCHK(hipMemsetAsync(head, 0, sizeof(RfHead), st));
     const long long ncol = (long long)qr->Ap0.size() - 1;
     if (deftol && ncol > 0) {
-        hipLaunchKernelGGL(k_rf_colnorm, dim3((unsigned)((ncol + RF_NT - 1) / RF_NT)), dim3(RF_NT), 0, st, ncol, X->ap.p,
-                           qr->is_lq ? X->tsrc.p : (const int *)nullptr, dAx, head);
-        HIPCHK(hipGetLastError());
+        HIPCHK((hipError_t)stm_launch_rf_colnorm(ncol, X->ap.p, qr->is_lq ? X->tsrc.p : (const int *)nullptr, dAx, &head->mx_bits, st));
     }
     if (maps && ny + nr1 > 0) {
         hipLaunchKernelGGL(k_rf_split, dim3((unsigned)((ny + nr1 + RF_NT - 1) / RF_NT)), dim3(RF_NT), 0, st, ny, nr1, X->ysrc.p, X->r1src.p, dAx,
@@ -227,6 +225,15 @@ int refactorize(stmmqr_qr *qr, const double *Ax, int ax_on_device)
 }
 
 }  // namespace
+
+// k_rf_colnorm for the library's other files (the damped least-squares object): mx_bits is the first member of the head
+int stm_launch_rf_colnorm(long long ncol, const long long *ap, const int *tsrc, const double *Ax, unsigned long long *mx_bits, hipStream_t st)
+{
+    static_assert(offsetof(RfHead, mx_bits) == 0, "the norm's bits lead the head");
+    if (ncol <= 0) return 0;
+    hipLaunchKernelGGL(k_rf_colnorm, dim3((unsigned)((ncol + RF_NT - 1) / RF_NT)), dim3(RF_NT), 0, st, ncol, ap, tsrc, Ax, (RfHead *)mx_bits);
+    return (int)hipGetLastError();
+}
 
 extern "C" int stmmqr_sparseqr_refactorize(stmmqr_qr *qr, const double *Ax, int ax_on_device)
 {
