@@ -939,6 +939,43 @@ int stmmqr_ls_solve_damped(stmmqr_ls *ls, const double *Ax, int ax_on_device, co
                            stm_long ldb, double *X, stm_long ldx, double *resid, int on_device);
 int stmmqr_ls_damped_info(const stmmqr_ls *ls, double *info /* [2] */);
 
+/* ---- The adjoint of the least-squares solve: the backward pass of x = argmin |C x - Bt| -----------------------------------------------
+ * (bilevel problems, learned weights and dampings, differentiable nonlinear least squares, the sensitivity of a fit to its data.)
+ * C = [W A; D] and Bt = [W B; 0] for a damped object, C = A and Bt = B for a plain one: the matrix whose values the LAST solve on the
+ * object factorized.  Given that solve's X (n x nrhs) and a cotangent Xbar = dL/dX (n x nrhs), with sums over the right-hand sides k:
+ *   z = (C'C)^-1 xbar = E R^-1 R^-T E' xbar over the live columns,   rt = Bt - C x,   ut = C z,
+ *   g(i, j) = sum_k rt[i,k] z[j,k] - ut[i,k] x[j,k]  for every stored entry (i, j) of C, the entries of D included,
+ *   Axbar[p] = w_i g(i, j) for entry p = (i, j) of A's storage (plain object, or w NULL: g),   Bbar = w o ut[0:m]  (m x nrhs),
+ *   wbar_i = 2 sum_k rt[i,k] ut[i,k] / w_i, and exactly 0.0 where w_i == 0 (the true value there is 2 w_i r_i (A z)_i = 0),
+ *   Dbar_j = g(m + j, j) = -2 D_jj sum_k x[j,k] z[j,k]: the gradient for the D_jj that the solve used.
+ * From Dbar a caller has dbar_j = sqrt(lambda) Dbar_j and lambdabar = -sum_j s_j^2 sum_k x[j,k] z[j,k] = sum_j s_j Dbar_j / (2 sqrt(lambda));
+ * the first form is finite at lambda = 0.
+ * Rank-deficient factors: the adjoint is that of the basic solution with the dead set held fixed, argmin |C(:, live) y - Bt|.  z is
+ * zero on dead columns (as R \ and the squeezed R' pass give it) and so is x: every gradient entry in a dead column is exactly 0.0.
+ * Accuracy: R^-1 R^-T squares the condition number, as in stmmqr_plan_solve_seminormal; `refine` has that call's meaning: refine times
+ * z += E R^-1 R^-T E' (xbar - C'(C z)), default 1.
+ * The call reads the factors and the values of the last solve.  It factorizes, analyses and plans nothing; the R' pass takes fronts of
+ * any width, so the call never returns STMMQR_ERR_TOO_LARGE for one; right-hand sides go in batches of STMMQR_RHS_BATCH.  Nothing in
+ * the library checks that X and w are those of the last solve: a caller who passes others gets the adjoint of nothing.  With
+ * scale = 1 in that solve the column scales depended on W A; Dbar is still the gradient for the D_jj used, and the gradients of Ax and
+ * w then lack the part that goes through the scales.
+ * Any output may be NULL and is then neither computed nor written.  on_device: X, Xbar, w and all outputs are device pointers (all of
+ * them, or none).  ldx, ldxb >= n, ldbb >= m.  The first call on a plain object uploads A's column pointers and row indices as int
+ * (anz + n + 1; counted in stmmqr_ls_info's device bytes, like every work buffer of this call).
+ * info [8] or NULL (a host array): [0] live columns among the first n, [1] refinement steps made, [2] the largest
+ * |xbar_k - C'C z_k| / |xbar_k| (0 where xbar_k = 0), [3] device ms of the call, [4] device ms of the two triangular passes alone,
+ * [5] device bytes the call added to the object, [6..7] 0.
+ * Refusals (STMMQR_ERR_INVALID, the message names the cause, nothing is written, the object stays usable): a null object, the host half
+ * only, no solve yet, a failed last solve, X or Xbar NULL or ldx < n or ldxb < n, Bbar given with ldbb < m, refine < 0, w, wbar or
+ * Dbar non-NULL on a plain object, a plan that does not hold the whole tree. */
+int stmmqr_ls_adjoint(stmmqr_ls *ls, const double *X, stm_long ldx, const double *Xbar, stm_long ldxb, const double *w, int refine,
+                      double *Axbar /* [anz] */, double *Bbar, stm_long ldbb /* m x nrhs */, double *wbar /* [m] */, double *Dbar /* [n] */,
+                      int on_device, double *info /* [8] or NULL */);
+/* the z = (C'C)^-1 xbar (n x nrhs, ldz >= n; zero on dead columns) of the last stmmqr_ls_adjoint call that succeeded, which the object
+ * keeps: with it lambdabar = -sum_j s_j^2 sum_k x[j,k] z[j,k] needs no division by sqrt(lambda).  Refuses (STMMQR_ERR_INVALID) before such
+ * a call, and Z NULL or ldz < n. */
+int stmmqr_ls_adjoint_z(stmmqr_ls *ls, double *Z, stm_long ldz, int on_device);
+
 void stmmqr_shutdown(void);                           /* optional end-of-use call for dlopen()ing hosts: device sync  */
 /* Device buffers for hosts without HIP bindings of their own (FFI callers of stmmqr_export_front_dev /
  * stmmqr_import_front_dev, device-resident A values): allocated by the HIP runtime THIS library is bound to, on the

@@ -1350,6 +1350,14 @@ lib.stmmqr_ls_solve_damped.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTE
                                        C.c_void_p, C.c_int]
 lib.stmmqr_ls_dims.argtypes = [C.c_void_p, c_long_p]
 lib.stmmqr_ls_damped_info.argtypes = [C.c_void_p, c_double_p]
+lib.stmmqr_ls_adjoint.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_long, C.c_void_p, C.c_void_p, C.c_int, c_double_p]
+lib.stmmqr_ls_adjoint_z.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int]
+_ADJOINT_INFO = ["live", "refine_steps", "normal_resid", "ms", "ms_passes", "bytes_added"]
+
+
+def _adjoint_info(v):
+    return dict(zip(_ADJOINT_INFO, v[:6].tolist()))
 
 
 class LeastSquares:
@@ -1438,6 +1446,47 @@ class LeastSquares:
             _check(lib.stmmqr_ls_resid(self._h, _dp(out)), "stmmqr_ls_resid")
             return out
         return None
+
+    def _adjoint_in(self, what, X, Xbar):
+        n, k = max(self.n, 1), self.nrhs
+        out = []
+        for name, a in (("X", X), ("Xbar", Xbar)):
+            a = np.asarray(a, np.float64)
+            if a.size != self.n * k:
+                raise StmmqrError(f"{what}: {name} must hold n x nrhs = {self.n} x {k} values")
+            f = np.zeros((n, k), order="F")
+            f[:self.n] = a.reshape(self.n, k)
+            out.append(f)
+        return out
+
+    def adjoint(self, X, Xbar, refine=1):
+        """after solve(): the backward pass of that solve (stmmqr_ls_adjoint).  X: the solution it returned, Xbar = dL/dX, both n x nrhs
+        (or vectors).  -> (Axbar [anz], the gradient on A's pattern; Bbar, shaped as B was; info).  Dead columns: exactly 0."""
+        Xf, Xb = self._adjoint_in("LeastSquares.adjoint", X, Xbar)
+        Axbar, Bbar, info = np.zeros(max(self.anz, 1)), np.zeros((max(self.m, 1), self.nrhs), order="F"), np.zeros(8)
+        _check(lib.stmmqr_ls_adjoint(self._h, Xf.ctypes.data, max(self.n, 1), Xb.ctypes.data, max(self.n, 1), None, int(refine),
+                                     Axbar.ctypes.data, Bbar.ctypes.data, max(self.m, 1), None, None, 0, _dp(info)), "stmmqr_ls_adjoint")
+        Bbar = Bbar[:self.m]
+        return Axbar[:self.anz], (Bbar[:, 0] if np.ndim(X) == 1 else Bbar), _adjoint_info(info)
+
+    def adjoint_dev(self, x_ptr: int, xbar_ptr: int, axbar_ptr=None, bbar_ptr=None, refine=1) -> dict:
+        """device pointers: X and Xbar (n x nrhs, ld n); where Axbar [anz] and Bbar (m x nrhs, ld m) go, None = not asked for.
+        Returns info."""
+        vp = lambda p: None if p is None else C.c_void_p(int(p))                                             # noqa: E731
+        info = np.zeros(8)
+        _check(lib.stmmqr_ls_adjoint(self._h, vp(x_ptr), max(self.n, 1), vp(xbar_ptr), max(self.n, 1), None, int(refine), vp(axbar_ptr),
+                                     vp(bbar_ptr), max(self.m, 1), None, None, 1, _dp(info)), "stmmqr_ls_adjoint")
+        return _adjoint_info(info)
+
+    def adjoint_z(self, dev_ptr=None):
+        """after adjoint(): its z = (C'C)^-1 xbar, n x nrhs, zero on dead columns (stmmqr_ls_adjoint_z).  dev_ptr: a device pointer
+        that receives it with leading dimension n (returns None)."""
+        if dev_ptr is not None:
+            _check(lib.stmmqr_ls_adjoint_z(self._h, C.c_void_p(int(dev_ptr)), max(self.n, 1), 1), "stmmqr_ls_adjoint_z")
+            return None
+        Z = np.zeros((max(self.n, 1), self.nrhs), order="F")
+        _check(lib.stmmqr_ls_adjoint_z(self._h, Z.ctypes.data, max(self.n, 1), 0), "stmmqr_ls_adjoint_z")
+        return Z[:self.n]
 
     def variances(self, dev_ptr=None):
         """after solve(): diag((A_live' A_live)^-1) in A's column order, 0 for dead columns (stmmqr_ls_covariance_diag).  dev_ptr: a
@@ -1563,6 +1612,36 @@ class DampedLeastSquares(LeastSquares):
         out = np.zeros(self.nrhs)
         _check(lib.stmmqr_ls_resid(self._h, _dp(out)), "stmmqr_ls_resid")
         return out
+
+    def adjoint(self, X, Xbar, w=None, refine=1):
+        """after solve(): the backward pass of that solve (stmmqr_ls_adjoint).  X: the solution it returned, Xbar = dL/dX, w: the
+        weights of that solve (None: all 1).  -> (Axbar [anz], Bbar as B was shaped, wbar [m], Dbar [n], info); Dbar is the gradient
+        for the D_jj used: dbar = sqrt(lam) * Dbar, lambdabar = sum_j s_j Dbar_j / (2 sqrt(lam)) (autograd.py has the form that is
+        finite at lam = 0)."""
+        Xf, Xb = self._adjoint_in("DampedLeastSquares.adjoint", X, Xbar)
+        wf = None
+        if w is not None:
+            wf = np.ascontiguousarray(w, np.float64).reshape(-1)
+            if wf.size != self.m:
+                raise StmmqrError(f"DampedLeastSquares.adjoint: w must hold {self.m} values")
+        Axbar, Bbar = np.zeros(max(self.anz, 1)), np.zeros((max(self.m, 1), self.nrhs), order="F")
+        wbar, Dbar, info = np.zeros(max(self.m, 1)), np.zeros(max(self.n, 1)), np.zeros(8)
+        _check(lib.stmmqr_ls_adjoint(self._h, Xf.ctypes.data, max(self.n, 1), Xb.ctypes.data, max(self.n, 1),
+                                     None if wf is None else wf.ctypes.data, int(refine), Axbar.ctypes.data, Bbar.ctypes.data, max(self.m, 1),
+                                     wbar.ctypes.data, Dbar.ctypes.data, 0, _dp(info)), "stmmqr_ls_adjoint")
+        Bbar = Bbar[:self.m]
+        return Axbar[:self.anz], (Bbar[:, 0] if np.ndim(X) == 1 else Bbar), wbar[:self.m], Dbar[:self.n], _adjoint_info(info)
+
+    def adjoint_dev(self, x_ptr: int, xbar_ptr: int, w_ptr=None, axbar_ptr=None, bbar_ptr=None, wbar_ptr=None, dbar_ptr=None,
+                    refine=1) -> dict:
+        """device pointers for every array: X and Xbar (n x nrhs, ld n), w [m] of the solve; where Axbar [anz], Bbar (m x nrhs, ld m),
+        wbar [m] and Dbar [n] go, None = not asked for.  Returns info."""
+        vp = lambda p: None if p is None else C.c_void_p(int(p))                                             # noqa: E731
+        info = np.zeros(8)
+        _check(lib.stmmqr_ls_adjoint(self._h, vp(x_ptr), max(self.n, 1), vp(xbar_ptr), max(self.n, 1), vp(w_ptr), int(refine),
+                                     vp(axbar_ptr), vp(bbar_ptr), max(self.m, 1), vp(wbar_ptr), vp(dbar_ptr), 1, _dp(info)),
+               "stmmqr_ls_adjoint")
+        return _adjoint_info(info)
 
     def diagnostics(self):
         """after solve(): (leverages [m + n], variances [n]) from ONE selected inversion (stmmqr_ls_leverage)"""

@@ -249,6 +249,21 @@ int stm_launch_lsb_diag(int n, const int *ap, const double *d, double sl, double
 int stm_launch_lsb_marquardt(int n, const int *ap, double sl, double smin, double smax, double *D, double *val, hipStream_t st);
 int stm_launch_lsb_rhs(long long m, long long n, int nrhs, const double *w, double *Bv, hipStream_t st);
 int stm_launch_lsb_dnorm(int n, int nrhs, const double *D, const double *X, long long ldx, double *out, hipStream_t st);
+// the adjoint of the least-squares solve (stmmqr_lsadjoint.hip).  entries: g(i, j) = sum_k rt[i,k] z[j,k] - ut[i,k] x[j,k] over A's
+// anz entries (ap / ai: A's int pattern; Axbar[p] = w[ai[p]] * g, w NULL = all 1) and over the n entries of D (row m + j; Dbar[j]);
+// entry (i, k) of rt / ut at i * si_r + k * sk_r, entry (j, k) of x / z at j * si_c + k * sk_c; a NULL output is skipped.  kfast:
+// out[i * nrhs + k] = in[i + k * ld], nrhs <= STMMQR_LS_MAX_NRHS.  pad: V (na x nb) = [s * src (n x nb, lds); 0], or with unit0 >= 0
+// row n + unit0 + k of column k = 1.  bbar: Bbar[i, k] = w[i] * ut[i, k].  wbar: 2 sum_k rt ut / w[i], 0.0 where w[i] == 0.  resid:
+// res = xbar - t per column, out[2k] = |res_k|^2, out[2k + 1] = |xbar_k|^2 (out may be NULL).
+int stm_launch_lsa_entries(long long anz, int n, long long m, int nrhs, const int *ap, const int *ai, const double *rt, const double *ut,
+                           long long si_r, long long sk_r, const double *x, const double *z, long long si_c, long long sk_c,
+                           const double *w, double *Axbar, double *Dbar, hipStream_t st);
+int stm_launch_lsa_kfast(long long rows, int nrhs, const double *in, long long ld, double *out, hipStream_t st);
+int stm_launch_lsa_pad(int n, int na, int nb, const double *src, long long lds, double s, int unit0, double *V, hipStream_t st);
+int stm_launch_lsa_bbar(long long m, int nrhs, const double *ut, long long ldu, const double *w, double *Bbar, long long ldbb, hipStream_t st);
+int stm_launch_lsa_wbar(long long m, int nrhs, const double *rt, const double *ut, long long ld, const double *w, double *wbar, hipStream_t st);
+int stm_launch_lsa_resid(int n, int nb, const double *xbar, long long ldxb, const double *t, long long ldt, double *res, long long ldr,
+                         double *out, hipStream_t st);
 // k_rf_colnorm (stmmqr_refactor.hip): the largest column 2-norm of the ncol columns ap (64-bit pointers) of Ax, bit for bit the one
 // stm_qr_default_tol takes, as the bits of a non-negative double combined into *mx_bits by an atomic maximum (mx_bits leads a block of
 // 16 bytes -- the refactorization's head -- which the caller zeroes first); tsrc: NULL, or the storage position of every entry

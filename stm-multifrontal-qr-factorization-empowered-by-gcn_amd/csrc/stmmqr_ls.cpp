@@ -6,6 +6,9 @@
 // (m + n) x n matrix [W A; D] with the right-hand sides [W B; 0].  A's columns are ordered as the plain object orders them, the
 // analysis is made once of the pattern [A; I | dense columns], and every solve builds the values on the device from
 // (Ax, w, d, lambda, B) with the kernels of stmmqr_lsbuild.hip: no host round trip, nothing analysed or planned again.
+// The adjoint (stmmqr_ls_adjoint): the backward pass of the last solve on either kind of object -- gradients on A's pattern, of B, w
+// and D -- from the resident factors: two triangular passes per normal solve, products with the plan's own matrix, the kernels of
+// stmmqr_lsadjoint.hip.
 #include <cfloat>
 #include <climits>
 #include <memory>
@@ -47,10 +50,29 @@ struct stmmqr_ls {
     {
         return 4.0 * (double)(d_ap.n + d_ai.n) + 8.0 * (double)(d_ap2.n + d_ax.n + d_D.n + d_head.n + d_w.n + d_x.n + d_dn.n);
     }
+    // ---- the adjoint (stmmqr_ls_adjoint): made by the first call, grown on demand, never shrunk.  The plain object's int pattern of
+    // A goes into d_ap / d_ai above at its first call (the damped object has it from create).
+    bool last_solve_ok = false;                         // the factors and d_val belong to a solve that came to its end
+    struct Adjoint {
+        DevBuf<double> x, xb, z;                        // n x nrhs: the solution, its cotangent, (C'C)^-1 xbar
+        DevBuf<double> v, t;                            // (n + nrhs) x nrhs: what the product with [C | Bt] takes / what its transpose gives
+        DevBuf<double> rt, ut;                          // rows of C x nrhs: Bt - C x, C z
+        DevBuf<double> y, cz, res, dz, nrm;             // per batch: R' \ in R's row order, C z, the refinement's residual and step; norms
+        DevBuf<double> xT, zT, rtT, utT;                // the four k-fastest (nrhs > 1)
+        DevBuf<double> o_ax, o_bb, o_wb, o_db;          // outputs of a call with host arrays
+        bool have_z = false;                            // z belongs to a call that came to its end (stmmqr_ls_adjoint_z)
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        double bytes() const
+        {
+            return 8.0 * (double)(x.n + xb.n + z.n + v.n + t.n + rt.n + ut.n + y.n + cz.n + res.n + dz.n + nrm.n + xT.n + zT.n + rtT.n + utT.n +
+                                  o_ax.n + o_bb.n + o_wb.n + o_db.n);
+        }
+    } adj;
     ~stmmqr_ls()
     {
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
         for (auto &e : ev_build) if (e) (void)hipEventDestroy(e);
+        for (auto &e : adj.ev) if (e) (void)hipEventDestroy(e);
         if (plan) stmmqr_plan_destroy(plan);
         if (sym) stmmqr_analysis_free(sym);
     }
@@ -222,6 +244,7 @@ int stmmqr_ls_solve(stmmqr_ls *ls, const double *Ax, int ax_on_device, const dou
     stmmqr_plan &P = *L.plan;
     HIPCHK(hipSetDevice(P.device));
     hipStream_t st = P.stream;
+    L.last_solve_ok = false;                               // (until this solve has come to its end: stmmqr_ls_adjoint)
     // ---- values [Ax | B] on the device; the tolerance follows the values of A ----
     try {
         if (Ax || !L.ax_current) {
@@ -273,6 +296,7 @@ int stmmqr_ls_solve(stmmqr_ls *ls, const double *Ax, int ax_on_device, const dou
     L.rank1 = 0;
     for (stm_long j = 0; j < n; j++) L.rank1 += !rd[(size_t)j];
     L.nsolves++;
+    L.last_solve_ok = true;
     return 0;
 }
 
@@ -297,6 +321,7 @@ static int ls_solve_damped_impl(stmmqr_ls *ls, const double *Ax, int ax_on_devic
     stmmqr_plan &P = *L.plan;
     HIPCHK(hipSetDevice(P.device));
     hipStream_t st = P.stream;
+    L.last_solve_ok = false;                               // (until this solve has come to its end: stmmqr_ls_adjoint)
     const hipMemcpyKind in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const hipMemcpyKind back = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     const double sl = std::sqrt(dmp->lambda);
@@ -377,6 +402,7 @@ static int ls_solve_damped_impl(stmmqr_ls *ls, const double *Ax, int ax_on_devic
     L.rank1 = 0;
     for (stm_long j = 0; j < n; j++) L.rank1 += !rd[(size_t)j];
     L.nsolves++;
+    L.last_solve_ok = true;
     return 0;
 }
 
@@ -388,6 +414,186 @@ int stmmqr_ls_solve_damped(stmmqr_ls *ls, const double *Ax, int ax_on_device, co
     } catch (const std::bad_alloc &) {
         return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_ls_solve_damped: out of memory");
     }
+}
+
+// The adjoint of the last solve; see include/stmmqr_hip.h.  z = E R11^-1 R11^-T E' xbar on the view of the R of [C | Bt] that ends at
+// column n (vectors zero beyond n, as the condition estimate has them: the leading rows of R' \ [v; 0] are R11' \ v and
+// R \ [y; 0] = R11 \ y), refined with products with the plan's own matrix: rt_k = [C | Bt] [-x_k; e_k], ut_k = [C | Bt] [z_k; 0], and
+// C'(C z) is the head of [C | Bt]' (C z).  Then the kernels of stmmqr_lsadjoint.hip.
+static int ls_adjoint_impl(stmmqr_ls *ls, const double *X, stm_long ldx, const double *Xbar, stm_long ldxb, const double *w, int refine,
+                           double *Axbar, double *Bbar, stm_long ldbb, double *wbar, double *Dbar, int on_device, double *info)
+{
+    const std::string F = "stmmqr_ls_adjoint: ";
+    if (!ls) return fail(STMMQR_ERR_INVALID, F + "null object");
+    if (!ls->plan) return fail(STMMQR_ERR_INVALID, F + "the object holds the host half only (device = -2 at create)");
+    if (ls->nsolves < 1) return fail(STMMQR_ERR_INVALID, F + "no solve yet");
+    if (!ls->last_solve_ok) return fail(STMMQR_ERR_INVALID, F + "the last solve failed (the factors belong to no solution)");
+    stmmqr_ls &L = *ls;
+    const stm_long am = L.damped ? L.am : L.m, mc = L.m, n = L.n, k = L.nrhs, na = n + k, aanz = L.damped ? L.aanz : L.anz;
+    if (!X || !Xbar) return fail(STMMQR_ERR_INVALID, F + "X or Xbar is NULL");
+    if (ldx < n || ldxb < n) return fail(STMMQR_ERR_INVALID, F + "a leading dimension of X or Xbar is smaller than n = " + std::to_string(n));
+    if (Bbar && ldbb < am) return fail(STMMQR_ERR_INVALID, F + "ldbb = " + std::to_string(ldbb) + " is smaller than m = " + std::to_string(am));
+    if (refine < 0) return fail(STMMQR_ERR_INVALID, F + "refine is negative");
+    if (!L.damped && (w || wbar || Dbar))
+        return fail(STMMQR_ERR_INVALID, F + "w, wbar and Dbar must be NULL on a plain object (stmmqr_ls_create)");
+    if (!L.damped && aanz >= INT_MAX) return fail(STMMQR_ERR_INVALID, F + "2^31 or more entries (the device table of A's rows is int)");
+    stmmqr_plan &P = *L.plan;
+    PASS(check_factored(&P));
+    PASS(check_carried_view(P, n));
+    if (!holds_whole_tree(P))
+        return fail(STMMQR_ERR_INVALID, F + "the plan does not hold the whole tree in one group (groups were set, or fronts are imported or shared)");
+    auto &A = L.adj;
+    auto &K = P.res.call;
+    const double bytes0 = L.damped_bytes() + A.bytes();
+    A.have_z = false;
+    PASS(begin_resident_op(P));
+    hipStream_t st = P.stream;
+    for (auto &e : A.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(A.ev[0], st));
+    HIPCHK(hipMemsetAsync(K.d_err.p, 0, sizeof(int), st));
+    PASS(ensure_rt(P, RT_SPLIT));
+    if (!L.d_ap.p) {                                        // the plain object's int pattern of A, once
+        std::vector<int> ap((size_t)n + 1), ai((size_t)std::max<stm_long>(aanz, 1), 0);
+        for (stm_long j = 0; j <= n; j++) ap[(size_t)j] = (int)L.Ap[(size_t)j];
+        for (stm_long p = 0; p < aanz; p++) ai[(size_t)p] = (int)L.Bi[(size_t)p];
+        LCHK(L.d_ap.alloc(ap.size()));
+        LCHK(L.d_ai.alloc(ai.size()));
+        HIPCHK(hipMemcpy(L.d_ap.p, ap.data(), ap.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(L.d_ai.p, ai.data(), ai.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    const double *dw = w;
+    if (w && !on_device) {
+        if (!L.d_w.p) LCHK(L.d_w.alloc((size_t)std::max<stm_long>(am, 1)));
+        if (am > 0) HIPCHK(hipMemcpyAsync(L.d_w.p, w, (size_t)am * sizeof(double), hipMemcpyHostToDevice, st));
+        dw = L.d_w.p;
+    }
+    // the live columns among the first n, in R's column order = the leading rows of R
+    std::vector<char> rd((size_t)std::max<stm_long>(n, 1), 0);
+    if (n > 0) HIPCHK(hipMemcpyAsync(rd.data(), P.d_Rdead.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    stm_long r = 0;
+    for (stm_long j = 0; j < n; j++) r += !rd[(size_t)j];
+    const size_t nn = (size_t)std::max<stm_long>(n, 1), mm = (size_t)std::max<stm_long>(mc, 1), kk = (size_t)k;
+    const size_t nbm = (size_t)std::min<stm_long>(rhs_batch_max(), k);
+    PASS(stage_in(A.x, X, ldx, n, k, on_device, st));
+    PASS(stage_in(A.xb, Xbar, ldxb, n, k, on_device, st));
+    LCHK(grow(A.x, nn * kk)); LCHK(grow(A.xb, nn * kk)); LCHK(grow(A.z, nn * kk));
+    LCHK(grow(A.v, (size_t)na * kk)); LCHK(grow(A.t, (size_t)na * nbm));
+    LCHK(grow(A.rt, mm * kk)); LCHK(grow(A.ut, mm * kk));
+    LCHK(grow(A.y, mm * nbm)); LCHK(grow(A.cz, mm * nbm)); LCHK(grow(A.res, nn * nbm)); LCHK(grow(A.dz, nn * nbm)); LCHK(grow(A.nrm, 2 * kk));
+    const int *qf = P.has_qfill ? P.res.sched.d_Qfill.p : nullptr;
+    double pass_ms = 0;
+    // out (n x nb) = E R11^-1 R11^-T E' rhs (n x nb), both with leading dimension n
+    auto normal_solve = [&](const double *rhs, double *out, int nb) -> int {
+        if (r == 0 || n == 0) { HIPCHK(hipMemsetAsync(out, 0, nn * (size_t)nb * sizeof(double), st)); return 0; }
+        HIPCHK(hipMemsetAsync(K.d_Xs.p, 0, (size_t)nb * (size_t)na * sizeof(double), st));
+        LCHK(stm_launch_perm(rhs, qf, K.d_Xs.p, (int)n, 0, st, nb, n, na));                      // b[j] = rhs[Qfill[j]], j < n; 0 beyond
+        HIPCHK(hipEventRecord(A.ev[2], st));
+        PASS(rt_pass(P, nb, RT_SPLIT));                                                         // R' \ b: the first r rows of d_Xr
+        HIPCHK(hipMemsetAsync(A.y.p, 0, mm * (size_t)nb * sizeof(double), st));
+        PASS(copy_cols(A.y.p, mc, K.d_Xr.p, mc, r, nb, hipMemcpyDeviceToDevice, st));
+        LCHK(stm_launch_perm(A.y.p, P.res.fact.d_Wmap.p, K.d_W.p, (int)mc, 0, st, nb, mc, mc));
+        PASS(rsolve_vector(P, nb));                                                             // R \ [y; 0] -> d_Xs
+        HIPCHK(hipEventRecord(A.ev[3], st));
+        LCHK(stm_launch_perm(K.d_Xs.p, qf, out, (int)n, 1, st, nb, na, n));                     // out[Qfill[j]] = x[j], j < n
+        HIPCHK(hipEventSynchronize(A.ev[3]));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, A.ev[2], A.ev[3]));
+        pass_ms += ms;
+        return 0;
+    };
+    // A.res (n x nb) = xb - C'(C z); nrm non-NULL: |res|^2 and |xb|^2 per column
+    auto residual = [&](const double *xb, const double *z, int nb, double *nrm) -> int {
+        LCHK(stm_launch_lsa_pad((int)n, (int)na, nb, z, n, 1.0, -1, A.v.p, st));
+        PASS(stmmqr_plan_spmv(&P, 0, A.v.p, std::max<stm_long>(na, 1), A.cz.p, (stm_long)mm, nb, 1));
+        PASS(stmmqr_plan_spmv(&P, 1, A.cz.p, (stm_long)mm, A.t.p, std::max<stm_long>(na, 1), nb, 1));
+        LCHK(stm_launch_lsa_resid((int)n, nb, xb, n, A.t.p, na, A.res.p, n, nrm, st));
+        return 0;
+    };
+    int steps = 0;
+    PASS(for_each_batch(P, k, [&](stm_long j0, int nb) -> int {
+        const double *xb = A.xb.p + j0 * n;
+        double *z = A.z.p + j0 * n;
+        PASS(normal_solve(xb, z, nb));
+        for (int it = 0; it < refine; it++) {
+            PASS(residual(xb, z, nb, nullptr));
+            PASS(normal_solve(A.res.p, A.dz.p, nb));
+            LCHK(stm_launch_add_cols((int)n, nb, A.dz.p, n, z, n, st));
+            if (j0 == 0) steps++;
+        }
+        if (info) PASS(residual(xb, z, nb, A.nrm.p + 2 * j0));
+        return 0;
+    }));
+    // rt = Bt - C x and ut = C z, all right-hand sides at once
+    LCHK(stm_launch_lsa_pad((int)n, (int)na, (int)k, A.z.p, n, 1.0, -1, A.v.p, st));
+    PASS(stmmqr_plan_spmv(&P, 0, A.v.p, std::max<stm_long>(na, 1), A.ut.p, (stm_long)mm, k, 1));
+    LCHK(stm_launch_lsa_pad((int)n, (int)na, (int)k, A.x.p, n, -1.0, 0, A.v.p, st));
+    PASS(stmmqr_plan_spmv(&P, 0, A.v.p, std::max<stm_long>(na, 1), A.rt.p, (stm_long)mm, k, 1));
+    // ---- the gradients ----
+    const hipMemcpyKind back = hipMemcpyDeviceToHost;
+    if (Bbar && am > 0) {
+        if (!on_device) LCHK(grow(A.o_bb, (size_t)am * kk));
+        LCHK(stm_launch_lsa_bbar(am, (int)k, A.ut.p, (long long)mm, dw, on_device ? Bbar : A.o_bb.p, on_device ? ldbb : am, st));
+        if (!on_device) PASS(copy_cols(Bbar, ldbb, A.o_bb.p, am, am, k, back, st));
+    }
+    if (wbar && am > 0) {
+        if (!on_device) LCHK(grow(A.o_wb, (size_t)am));
+        LCHK(stm_launch_lsa_wbar(am, (int)k, A.rt.p, A.ut.p, (long long)mm, dw, on_device ? wbar : A.o_wb.p, st));
+        if (!on_device) HIPCHK(hipMemcpyAsync(wbar, A.o_wb.p, (size_t)am * sizeof(double), back, st));
+    }
+    double *gA = (Axbar && aanz > 0) ? Axbar : nullptr, *gD = (Dbar && n > 0) ? Dbar : nullptr;
+    if (gA || gD) {
+        const double *x = A.x.p, *z = A.z.p, *rt = A.rt.p, *ut = A.ut.p;
+        long long si = 1, sk_r = (long long)mm, sk_c = (long long)n;
+        if (k > 1) {                                        // the four vectors k-fastest
+            LCHK(grow(A.xT, nn * kk)); LCHK(grow(A.zT, nn * kk)); LCHK(grow(A.rtT, mm * kk)); LCHK(grow(A.utT, mm * kk));
+            LCHK(stm_launch_lsa_kfast(n, (int)k, x, n, A.xT.p, st));
+            LCHK(stm_launch_lsa_kfast(n, (int)k, z, n, A.zT.p, st));
+            LCHK(stm_launch_lsa_kfast(mc, (int)k, rt, (long long)mm, A.rtT.p, st));
+            LCHK(stm_launch_lsa_kfast(mc, (int)k, ut, (long long)mm, A.utT.p, st));
+            x = A.xT.p; z = A.zT.p; rt = A.rtT.p; ut = A.utT.p;
+            si = k; sk_r = sk_c = 1;
+        }
+        if (gA && !on_device) { LCHK(grow(A.o_ax, (size_t)aanz)); gA = A.o_ax.p; }
+        if (gD && !on_device) { LCHK(grow(A.o_db, nn)); gD = A.o_db.p; }
+        LCHK(stm_launch_lsa_entries(aanz, (int)n, am, (int)k, L.d_ap.p, L.d_ai.p, rt, ut, si, sk_r, x, z, si, sk_c, dw, gA, gD, st));
+        if (gA && !on_device) HIPCHK(hipMemcpyAsync(Axbar, gA, (size_t)aanz * sizeof(double), back, st));
+        if (gD && !on_device) HIPCHK(hipMemcpyAsync(Dbar, gD, (size_t)n * sizeof(double), back, st));
+    }
+    std::vector<double> nr(2 * kk, 0.0);
+    if (info) HIPCHK(hipMemcpyAsync(nr.data(), A.nrm.p, nr.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(A.ev[1], st));
+    PASS(end_resident_op(P));
+    A.have_z = true;
+    if (info) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, A.ev[0], A.ev[1]));
+        double worst = 0;
+        for (size_t j = 0; j < kk; j++)
+            if (nr[2 * j + 1] > 0) worst = std::max(worst, std::sqrt(nr[2 * j] / nr[2 * j + 1]));
+        info[0] = (double)r; info[1] = (double)steps; info[2] = worst; info[3] = ms; info[4] = pass_ms;
+        info[5] = L.damped_bytes() + A.bytes() - bytes0; info[6] = info[7] = 0;
+    }
+    return 0;
+}
+
+int stmmqr_ls_adjoint(stmmqr_ls *ls, const double *X, stm_long ldx, const double *Xbar, stm_long ldxb, const double *w, int refine,
+                      double *Axbar, double *Bbar, stm_long ldbb, double *wbar, double *Dbar, int on_device, double *info)
+{
+    try {
+        return ls_adjoint_impl(ls, X, ldx, Xbar, ldxb, w, refine, Axbar, Bbar, ldbb, wbar, Dbar, on_device, info);
+    } catch (const std::bad_alloc &) {
+        return stm_fail(STMMQR_ERR_OUT_OF_MEMORY, "stmmqr_ls_adjoint: out of memory");
+    }
+}
+
+// the z = (C'C)^-1 xbar of the last stmmqr_ls_adjoint call, which the object keeps (what lambdabar is made of)
+int stmmqr_ls_adjoint_z(stmmqr_ls *ls, double *Z, stm_long ldz, int on_device)
+{
+    if (!ls || !ls->plan || !ls->adj.have_z) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_adjoint_z: no adjoint call yet on this object");
+    if (!Z || ldz < ls->n) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_adjoint_z: Z is NULL or ldz < n");
+    HIPCHK(hipSetDevice(ls->plan->device));
+    return stage_out(ls->adj.z, Z, ldz, ls->n, ls->nrhs, on_device, ls->plan->stream);
 }
 
 int stmmqr_ls_dims(const stmmqr_ls *ls, stm_long *dims)
@@ -413,7 +619,7 @@ int stmmqr_ls_info(const stmmqr_ls *ls, double *info)
     if (!ls || !info) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_info: null argument");
     const stm_qr_symbolic *S = stmmqr_analysis_symbolic(ls->sym);
     info[0] = (double)ls->rank1; info[1] = (double)S->nf; info[2] = ls->stats.flops; info[3] = ls->sym_info[0];
-    info[4] = ls->stats.ms_total; info[5] = ls->solve_ms; info[6] = ls->stats.device_bytes + (double)ls->d_val.n * sizeof(double) + ls->damped_bytes();
+    info[4] = ls->stats.ms_total; info[5] = ls->solve_ms; info[6] = ls->stats.device_bytes + (double)ls->d_val.n * sizeof(double) + ls->damped_bytes() + ls->adj.bytes();
     info[7] = (double)ls->stats.retries; info[8] = (double)ls->stats.reschedules;
     info[9] = (double)ls->nanalyses; info[10] = (double)ls->nplans; info[11] = (double)ls->nsolves;
     info[12] = ls->tol; info[13] = (double)ls->nrhs;
