@@ -976,6 +976,68 @@ int stmmqr_ls_adjoint(stmmqr_ls *ls, const double *X, stm_long ldx, const double
  * a call, and Z NULL or ldz < n. */
 int stmmqr_ls_adjoint_z(stmmqr_ls *ls, double *Z, stm_long ldz, int on_device);
 
+/* ---- Robust least squares: iteratively reweighted solves with row multipliers made from the residual on the device ----------------------
+ * (outliers in bundle adjustment, pose graphs, geodesy, regression.)  min_x sum_i rho(|w0_i r_i| / sigma) with r = b - A x, as the fixed
+ * point of weighted solves: from x, the UNWEIGHTED residual r (A's values as given -- the damped object's unweighted copy, the values of
+ * create, or the Ax of the call; never the weighted values a solve built), a_i = |w0_i r_i| (one product), the scale
+ * sigma = max(mad_factor * median(a_i : w0_i != 0), sigma_min) or a given one, u_i = a_i / sigma, and the row multiplier
+ * w_i = w0_i f(u_i) with f = sqrt(psi(u) / u) (the object's w multiplies the residual).  loss, f(u), rho(u), default cc:
+ *   0 L2       1                              u^2 / 2                                              --
+ *   1 Huber    u <= cc ? 1 : sqrt(cc / u)     u <= cc ? u^2 / 2 : cc (u - cc / 2)                  1.345
+ *   2 Cauchy   1 / sqrt(1 + (u/cc)^2)         (cc^2 / 2) log(1 + (u/cc)^2)                         2.3849
+ *   3 Tukey    u < cc ? 1 - (u/cc)^2 : 0      u < cc ? (cc^2 / 6)(1 - (1 - (u/cc)^2)^3) : cc^2 / 6 4.6851
+ *   4 L1       1 / sqrt(max(u, cc))           u >= cc ? u : u^2 / (2 cc) + cc / 2                  none (smoothed below cc: cc > 0 required)
+ * The median is exact: the two middle order statistics lo = a_(floor((c-1)/2)) and hi = a_(floor(c/2)) of the c rows with w0_i != 0 by a
+ * radix select on the device, 0.5 * (lo + hi).  sigma == 0 after the floor (an exact fit): w = w0, loss = 0, flag 1; no division by zero
+ * is formed.  The sum of rho runs over all m rows in a fixed order: the same bits run after run.  NaN in the data is not searched for.
+ * The first call on an object builds the row form of A on the host (m + 1 + 2 anz ints) and uploads it with the work vectors; all of it
+ * is counted in stmmqr_ls_info's device bytes (and reported in info[7] below).
+ * stmmqr_median_abs needs no object: the median of |v_i| (mask NULL) or of |mask_i * v_i| over the entries with mask_i != 0;
+ * out[0] = 0.5 * (lo + hi), out[1] = lo, out[2] = hi, out[3] = the count; count == 0: out[0..2] = 0.  on_device: v, mask and out are
+ * device pointers.
+ * stmmqr_ls_robust_weights: one reweighting from a given X [n] on either kind of object (nrhs of the object must be 1): r_out [m] and
+ * w_out [m], either may be NULL.  Ax NULL: the values given at create; ax_on_device as in the solves; on_device: B, X, rb->w0, r_out, w_out
+ * are device pointers (all of them, or none).  stat [8], a host array or NULL: sigma, lo, hi, count (lo, hi, count 0 with a given sigma),
+ * the sum of rho, rows rejected (w_i == 0 although w0_i != 0), rows with f == 1, flags (1: sigma was 0).
+ * stmmqr_ls_solve_robust, the loop: x0 NULL: the first solve uses w0 alone (the L2 start); else the first weights come from x0.  Every
+ * further solve is preceded by a reweighting from the last x.  It stops after the first solve whose step satisfies
+ * max_j |x_j - xprev_j| <= rtol * max_j |x_j| (the first solve without x0 has no step), or at max_iter solves.  sigma_iters >= 0 (with
+ * rb->sigma == 0): the scale is estimated in the first max(sigma_iters, 1) reweightings and frozen afterwards; < 0: every time.
+ * A damped object takes its damping in dmp (dmp->w must be NULL: prior weights go in rb->w0; d, D_out, dnorm host or device with
+ * on_device) and every solve is stmmqr_ls_solve_damped with the device w; a plain object takes dmp NULL, and every solve is
+ * stmmqr_ls_solve of the values w[Ai[p]] * Ax[p] and the right-hand side w o b, one multiplication each -- afterwards the object's
+ * values are weighted ones, and a later stmmqr_ls_solve with Ax NULL uploads the values of create again.  With host arrays the inputs
+ * go up once and the outputs come down once; between two solves only the eight statistics and the two maxima of the step reach the host.
+ * X [n], w_out [m] or NULL: the multipliers of the LAST solve, resid [1] or NULL: that solve's residual norm.  hist [4 * max_iter] or
+ * NULL, a host array, per solve: sigma and sum of rho of the reweighting that made its weights (0, 0 for a first solve from w0 alone),
+ * the step max |x - xprev| (infinity where there is none), the solve's residual norm.  info [8] or NULL, a host array: solves made,
+ * converged (0 / 1), the last step over max |x|, sigma, sum of rho and rows rejected of the last reweighting, device ms of the
+ * reweightings alone, device bytes this feature holds.
+ * After the call the factors are those of the last solve: stmmqr_ls_covariance_diag, _leverage, _condest and the R export work
+ * unchanged, on W A (or [W A; D]) with the final weights, and on a damped object stmmqr_ls_adjoint works with w = w_out -- the adjoint
+ * with the weights HELD FIXED, not the derivative through the fixed point.
+ * Refusals (STMMQR_ERR_INVALID, the message names the cause, nothing is written, the object stays usable; all decided before any device
+ * work): a null object, an object created with nrhs != 1, rb NULL, loss outside 0 .. 4, sigma, sigma_min, cc or mad_factor not finite,
+ * sigma < 0 or sigma_min < 0, L1 with cc <= 0, max_iter < 1, rtol negative or NaN, dmp given on a plain object or missing on a damped
+ * one, dmp->w non-NULL (and what stmmqr_ls_solve_damped refuses of dmp), B or X NULL, the host half only.  A solve that fails inside
+ * the loop returns its code and leaves the object usable.
+ * stmmqr_ls_robust_times: ms [4] = device ms of the last reweighting's residual (with |w0 o r|), selection, weights, and their sum. */
+int stmmqr_median_abs(const double *v, const double *mask, stm_long len, int device, int on_device, double *out /* [4] */);
+typedef struct {
+    int loss;              /* 0 .. 4 above */
+    double cc;             /* tuning constant; <= 0: the default of the loss (L1 has none: refused) */
+    double sigma;          /* > 0: fixed scale; 0: sigma = mad_factor * median |w0_i r_i| over w0_i != 0 */
+    double mad_factor;     /* <= 0: 1.4826 */
+    double sigma_min;      /* >= 0: floor of the scale */
+    const double *w0;      /* [m] prior row multipliers (inverse standard deviations), NULL: all 1 */
+} stmmqr_ls_robust;
+int stmmqr_ls_robust_weights(stmmqr_ls *ls, const double *Ax, int ax_on_device, const stmmqr_ls_robust *rb, const double *B,
+                             const double *X, double *r_out, double *w_out, int on_device, double *stat /* [8] */);
+int stmmqr_ls_solve_robust(stmmqr_ls *ls, const double *Ax, int ax_on_device, const stmmqr_ls_robust *rb, const stmmqr_ls_damping *dmp,
+                           const double *B, const double *x0, int max_iter, double rtol, int sigma_iters,
+                           double *X, double *w_out, double *resid, int on_device, double *hist, double *info);
+int stmmqr_ls_robust_times(const stmmqr_ls *ls, double *ms /* [4] */);
+
 void stmmqr_shutdown(void);                           /* optional end-of-use call for dlopen()ing hosts: device sync  */
 /* Device buffers for hosts without HIP bindings of their own (FFI callers of stmmqr_export_front_dev /
  * stmmqr_import_front_dev, device-resident A values): allocated by the HIP runtime THIS library is bound to, on the

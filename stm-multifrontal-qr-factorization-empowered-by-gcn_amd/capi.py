@@ -1356,6 +1356,61 @@ lib.stmmqr_ls_adjoint_z.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int]
 _ADJOINT_INFO = ["live", "refine_steps", "normal_resid", "ms", "ms_passes", "bytes_added"]
 
 
+class LsRobust(C.Structure):
+    """stmmqr_ls_robust (include/stmmqr_hip.h)"""
+    _fields_ = [("loss", C.c_int), ("cc", C.c_double), ("sigma", C.c_double), ("mad_factor", C.c_double), ("sigma_min", C.c_double),
+                ("w0", C.c_void_p)]
+
+
+ROBUST_LOSSES = {"l2": 0, "huber": 1, "cauchy": 2, "tukey": 3, "l1": 4}
+lib.stmmqr_median_abs.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]
+lib.stmmqr_ls_robust_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LsRobust), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int, c_double_p]
+lib.stmmqr_ls_solve_robust.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LsRobust), C.POINTER(LsDamping), C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, c_double_p, c_double_p]
+lib.stmmqr_ls_robust_times.argtypes = [C.c_void_p, c_double_p]
+_ROBUST_STAT = ["sigma", "lo", "hi", "count", "loss", "rejected", "unit", "flags"]
+_ROBUST_INFO = ["solves", "converged", "step_ratio", "sigma", "loss", "rejected", "ms_reweight", "robust_bytes"]
+
+
+def median_abs(v, mask=None, device=-1):
+    """the exact median of |v| (mask None) or of |mask * v| over the entries with mask != 0, found on the device by a radix select
+    (stmmqr_median_abs) -> {"median": 0.5 * (lo + hi), "lo", "hi", "count"}; all 0 for no entry"""
+    v = np.ascontiguousarray(v, np.float64).reshape(-1)
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, np.float64).reshape(-1)
+        if mask.size != v.size:
+            raise StmmqrError("median_abs: mask must hold one value per entry of v")
+    out = np.zeros(4)
+    _check(lib.stmmqr_median_abs(v.ctypes.data if v.size else None, None if mask is None else mask.ctypes.data, v.size, int(device), 0,
+                                 out.ctypes.data), "stmmqr_median_abs")
+    return {"median": float(out[0]), "lo": float(out[1]), "hi": float(out[2]), "count": int(out[3])}
+
+
+def median_abs_dev(v_ptr: int, length: int, out_ptr: int, mask_ptr=None, device=-1):
+    """device pointers: v [length], mask [length] or None, out [4] receives the median, lo, hi and the count"""
+    _check(lib.stmmqr_median_abs(C.c_void_p(int(v_ptr)), None if mask_ptr is None else C.c_void_p(int(mask_ptr)), int(length), int(device),
+                                 1, C.c_void_p(int(out_ptr))), "stmmqr_median_abs")
+
+
+def _robust_rule(loss, cc, sigma, mad_factor, sigma_min, w0_ptr):
+    if isinstance(loss, str):
+        if loss not in ROBUST_LOSSES:
+            raise StmmqrError(f"robust fit: unknown loss {loss!r} (one of {sorted(ROBUST_LOSSES)})")
+        loss = ROBUST_LOSSES[loss]
+    return LsRobust(int(loss), 0.0 if cc is None else float(cc), float(sigma), float(mad_factor), float(sigma_min), w0_ptr)
+
+
+def _robust_info(info, hist, resid=None):
+    d = dict(zip(_ROBUST_INFO, info.tolist()))
+    d["solves"], d["converged"] = int(d["solves"]), bool(d["converged"])
+    d["hist"] = hist[:d["solves"]].copy()                  # per solve: sigma, loss, step, resid
+    if resid is not None:
+        d["resid"] = float(resid[0])
+    return d
+
+
+
 def _adjoint_info(v):
     return dict(zip(_ADJOINT_INFO, v[:6].tolist()))
 
@@ -1548,6 +1603,86 @@ class LeastSquares:
                "stmmqr_ls_covariance_entries")
         return out[:I.size]
 
+    def _vec(self, what, name, a, size):
+        a = np.ascontiguousarray(a, np.float64).reshape(-1)
+        if a.size != size:
+            raise StmmqrError(f"{what}: {name} must hold {size} values")
+        return a
+
+    def robust_weights(self, B, X, loss="huber", cc=None, sigma=0.0, w0=None, mad_factor=0.0, sigma_min=0.0, Ax=None):
+        """one reweighting of a robust fit from a given x (stmmqr_ls_robust_weights; nrhs must be 1) -> (r, w, stat): the unweighted
+        residual b - A x, the row multipliers w = w0 * f(|w0 r| / sigma), and sigma, lo, hi, count, loss, rejected, unit, flags.
+        sigma = 0: mad_factor * median |w0 r| over w0 != 0, floored at sigma_min."""
+        what = type(self).__name__ + ".robust_weights"
+        keep = {"B": self._vec(what, "B", B, self.m), "X": self._vec(what, "X", X, self.n)}
+        if w0 is not None:
+            keep["w0"] = self._vec(what, "w0", w0, self.m)
+        if Ax is not None:
+            keep["Ax"] = self._vec(what, "Ax", Ax, self.anz)
+        ptr = lambda k: keep[k].ctypes.data if k in keep else None                                           # noqa: E731
+        rb = _robust_rule(loss, cc, sigma, mad_factor, sigma_min, ptr("w0"))
+        r, w, stat = np.zeros(max(self.m, 1)), np.zeros(max(self.m, 1)), np.zeros(8)
+        _check(lib.stmmqr_ls_robust_weights(self._h, ptr("Ax"), 0, C.byref(rb), ptr("B"), ptr("X"), r.ctypes.data, w.ctypes.data, 0,
+                                            _dp(stat)), "stmmqr_ls_robust_weights")
+        return r[:self.m], w[:self.m], dict(zip(_ROBUST_STAT, stat.tolist()))
+
+    def robust_weights_dev(self, b_ptr: int, x_ptr: int, r_ptr=None, w_ptr=None, loss="huber", cc=None, sigma=0.0, w0_ptr=None,
+                           mad_factor=0.0, sigma_min=0.0, ax_ptr=None) -> dict:
+        """device pointers: B [m], X [n], optionally w0 [m] and A's values; where r [m] and w [m] go, None = not asked for.  Returns stat."""
+        vp = lambda p: None if p is None else C.c_void_p(int(p))                                             # noqa: E731
+        rb = _robust_rule(loss, cc, sigma, mad_factor, sigma_min, None if w0_ptr is None else int(w0_ptr))
+        stat = np.zeros(8)
+        _check(lib.stmmqr_ls_robust_weights(self._h, vp(ax_ptr), 1, C.byref(rb), vp(b_ptr), vp(x_ptr), vp(r_ptr), vp(w_ptr), 1, _dp(stat)),
+               "stmmqr_ls_robust_weights")
+        return dict(zip(_ROBUST_STAT, stat.tolist()))
+
+    def robust_times(self) -> dict:
+        """device ms of the last reweighting: residual, selection, weights, and their sum (stmmqr_ls_robust_times)"""
+        v = np.zeros(4)
+        _check(lib.stmmqr_ls_robust_times(self._h, _dp(v)), "stmmqr_ls_robust_times")
+        return dict(zip(["residual", "selection", "weights", "total"], v.tolist()))
+
+    def _solve_robust(self, dmp, keep, B, loss, cc, sigma, w0, x0, max_iter, rtol, sigma_iters, Ax, mad_factor, sigma_min):
+        what = type(self).__name__ + ".solve_robust"
+        keep["B"] = self._vec(what, "B", B, self.m)
+        for name, a, size in (("w0", w0, self.m), ("x0", x0, self.n), ("Ax", Ax, self.anz)):
+            if a is not None:
+                keep[name] = self._vec(what, name, a, size)
+        ptr = lambda k: keep[k].ctypes.data if k in keep else None                                           # noqa: E731
+        rb = _robust_rule(loss, cc, sigma, mad_factor, sigma_min, ptr("w0"))
+        X, w, resid = np.zeros(max(self.n, 1)), np.zeros(max(self.m, 1)), np.zeros(1)
+        hist, info = np.zeros((max(int(max_iter), 1), 4)), np.zeros(8)
+        _check(lib.stmmqr_ls_solve_robust(self._h, ptr("Ax"), 0, C.byref(rb), None if dmp is None else C.byref(dmp), ptr("B"), ptr("x0"),
+                                          int(max_iter), float(rtol), int(sigma_iters), X.ctypes.data, w.ctypes.data, resid.ctypes.data, 0,
+                                          _dp(hist), _dp(info)), "stmmqr_ls_solve_robust")
+        return X[:self.n], w[:self.m], _robust_info(info, hist, resid)
+
+    def _solve_robust_dev(self, dmp, b_ptr, x_ptr, w_ptr, loss, cc, sigma, w0_ptr, x0_ptr, max_iter, rtol, sigma_iters, ax_ptr, mad_factor,
+                          sigma_min, resid_ptr):
+        vp = lambda p: None if p is None else C.c_void_p(int(p))                                             # noqa: E731
+        rb = _robust_rule(loss, cc, sigma, mad_factor, sigma_min, None if w0_ptr is None else int(w0_ptr))
+        hist, info = np.zeros((max(int(max_iter), 1), 4)), np.zeros(8)
+        _check(lib.stmmqr_ls_solve_robust(self._h, vp(ax_ptr), 1, C.byref(rb), None if dmp is None else C.byref(dmp), vp(b_ptr), vp(x0_ptr),
+                                          int(max_iter), float(rtol), int(sigma_iters), vp(x_ptr), vp(w_ptr), vp(resid_ptr), 1, _dp(hist),
+                                          _dp(info)), "stmmqr_ls_solve_robust")
+        return _robust_info(info, hist)
+
+    def solve_robust(self, B, loss="huber", cc=None, sigma=0.0, w0=None, x0=None, max_iter=50, rtol=1e-8, sigma_iters=-1, Ax=None,
+                     mad_factor=0.0, sigma_min=0.0):
+        """a robust fit by iteratively reweighted solves, everything between two solves on the device (stmmqr_ls_solve_robust; nrhs
+        must be 1) -> (X, w, info): the solution, the row multipliers of the last solve, and solves, converged, step_ratio, sigma,
+        loss, rejected, ms_reweight, robust_bytes, resid and hist (per solve: sigma, loss, step, resid).  loss: "l2", "huber",
+        "cauchy", "tukey", "l1" (or 0 .. 4); cc None: the default of the loss; sigma = 0: the MAD of the residuals, re-estimated in
+        the first sigma_iters reweightings (< 0: always); w0: prior row multipliers; x0: where the first weights come from (None: the
+        L2 start).  Every solve is solve(w * b, Ax = w[Ai] * Ax): afterwards the object's values are weighted ones."""
+        return self._solve_robust(None, {}, B, loss, cc, sigma, w0, x0, max_iter, rtol, sigma_iters, Ax, mad_factor, sigma_min)
+
+    def solve_robust_dev(self, b_ptr: int, x_ptr: int, w_ptr=None, loss="huber", cc=None, sigma=0.0, w0_ptr=None, x0_ptr=None, max_iter=50,
+                         rtol=1e-8, sigma_iters=-1, ax_ptr=None, mad_factor=0.0, sigma_min=0.0, resid_ptr=None) -> dict:
+        """device pointers: B [m], where X [n] and w [m] go, optionally w0 [m], x0 [n], A's values, resid [1].  Returns info."""
+        return self._solve_robust_dev(None, b_ptr, x_ptr, w_ptr, loss, cc, sigma, w0_ptr, x0_ptr, max_iter, rtol, sigma_iters, ax_ptr,
+                                      mad_factor, sigma_min, resid_ptr)
+
     def std_errors(self) -> np.ndarray:
         """after solve(): the standard errors of x, n x nrhs: sqrt(var * resid_j^2 / (m - rank)) for right-hand side j; inf where
         m == rank (no degree of freedom left)."""
@@ -1659,6 +1794,29 @@ class DampedLeastSquares(LeastSquares):
         lev = np.zeros(max(self.m + self.n, 1))
         _check(lib.stmmqr_ls_leverage(self._h, lev.ctypes.data, None, 0), "stmmqr_ls_leverage")
         return lev[:self.m + self.n]
+
+    def solve_robust(self, B, loss="huber", cc=None, sigma=0.0, w0=None, x0=None, max_iter=50, rtol=1e-8, sigma_iters=-1, Ax=None,
+                     mad_factor=0.0, sigma_min=0.0, d=None, lam=0.0, scale=0, scale_min=1e-6, scale_max=1e32):
+        """LeastSquares.solve_robust with the damping of solve(): every solve is solve(w=...) with the device's multipliers.  info also
+        holds dnorm and D of the last solve."""
+        keep = {}
+        if d is not None:
+            keep["d"] = self._vec("DampedLeastSquares.solve_robust", "d", d, self.n)
+        dnorm, D = np.zeros(1), np.zeros(max(self.n, 1))
+        dmp = self._damping(None, keep["d"].ctypes.data if d is not None else None, lam, scale, scale_min, scale_max, D.ctypes.data,
+                            dnorm.ctypes.data)
+        X, w, info = self._solve_robust(dmp, keep, B, loss, cc, sigma, w0, x0, max_iter, rtol, sigma_iters, Ax, mad_factor, sigma_min)
+        info["dnorm"], info["D"] = float(dnorm[0]), D[:self.n]
+        return X, w, info
+
+    def solve_robust_dev(self, b_ptr: int, x_ptr: int, w_ptr=None, loss="huber", cc=None, sigma=0.0, w0_ptr=None, x0_ptr=None, max_iter=50,
+                         rtol=1e-8, sigma_iters=-1, ax_ptr=None, mad_factor=0.0, sigma_min=0.0, resid_ptr=None, d_ptr=None, lam=0.0,
+                         scale=0, scale_min=1e-6, scale_max=1e32, dnorm_ptr=None, D_ptr=None) -> dict:
+        """device pointers for every array, the damping's d [n], dnorm [1] and D [n] included.  Returns info."""
+        vp = lambda p: None if p is None else int(p)                                                          # noqa: E731
+        dmp = self._damping(None, vp(d_ptr), lam, scale, scale_min, scale_max, vp(D_ptr), vp(dnorm_ptr))
+        return self._solve_robust_dev(dmp, b_ptr, x_ptr, w_ptr, loss, cc, sigma, w0_ptr, x0_ptr, max_iter, rtol, sigma_iters, ax_ptr,
+                                      mad_factor, sigma_min, resid_ptr)
 
     def std_errors(self):
         raise StmmqrError("DampedLeastSquares.std_errors: not defined for a damped fit (use variances() and the residuals)")

@@ -13,6 +13,7 @@
 //   stmmqr_nullspace.hip null-space basis of R: Gram matrix, Cholesky factorization, the minimum-norm projector
 //   stmmqr_lsbuild.hip   the values of [W A; D | W B; 0] of the damped least-squares object, |D x|
 //   stmmqr_lsadjoint.hip the adjoint of the least-squares solve: gradients on A's pattern, of B, w and D
+//   stmmqr_lsrobust.hip  robust fits: the unweighted residual by rows, the exact median by radix select, the weight functions
 // (stmmqr_capanel.hip: the Gram-based panel.)  Kernels are compiled one by one, so the split changes no kernel's code.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -264,6 +264,23 @@ int stm_launch_lsa_bbar(long long m, int nrhs, const double *ut, long long ldu, 
 int stm_launch_lsa_wbar(long long m, int nrhs, const double *rt, const double *ut, long long ld, const double *w, double *wbar, hipStream_t st);
 int stm_launch_lsa_resid(int n, int nb, const double *xbar, long long ldxb, const double *t, long long ldt, double *res, long long ldr,
                          double *out, hipStream_t st);
+// robust least squares (stmmqr_lsrobust.hip).  resid: r = b - A x over the row form (rp, rj, rq) with the values Ax.  abs: a = |w0 o r|
+// (w0 NULL: |r|).  select: the order statistics of a over mask != 0 (mask NULL: all) -- out[0..3] = 0.5 (lo + hi), lo, hi, the count, on
+// the device; sel: stm_lsr_sel_words() words, zeroed by the call.  weights: w = w0 o f(a / sigma) and stat[0..7] = sigma, lo, hi, count,
+// sum of rho, rows rejected, rows with f == 1, flags, with sigma = max(med ? mad_factor * med[0] : sigma_given, sigma_min) (med: what
+// select wrote); part: stm_lsr_part_doubles(m) doubles.  step: out[0] = max |x - xprev|, out[1] = max |x|.  scale: dst[p] =
+// w[idx[p]] * src[p] (idx NULL: w[p]).  fill: dst[p] = v.
+long long stm_lsr_sel_words();
+long long stm_lsr_part_doubles(long long m);
+int stm_launch_lsr_resid(long long m, const int *rp, const int *rj, const int *rq, const double *Ax, const double *x, const double *b,
+                         double *r, hipStream_t st);
+int stm_launch_lsr_abs(long long m, const double *w0, const double *r, double *a, hipStream_t st);
+int stm_launch_lsr_select(long long len, const double *a, const double *mask, unsigned long long *sel, double *out, hipStream_t st);
+int stm_launch_lsr_weights(long long m, const double *a, const double *w0, const double *med, double sigma_given, double mad_factor,
+                           double sigma_min, int loss, double cc, double *w, double *part, double *stat, hipStream_t st);
+int stm_launch_lsr_step(long long n, const double *x, const double *xprev, double *out, hipStream_t st);
+int stm_launch_lsr_scale(long long len, const int *idx, const double *w, const double *src, double *dst, hipStream_t st);
+int stm_launch_lsr_fill(long long len, double v, double *dst, hipStream_t st);
 // k_rf_colnorm (stmmqr_refactor.hip): the largest column 2-norm of the ncol columns ap (64-bit pointers) of Ax, bit for bit the one
 // stm_qr_default_tol takes, as the bits of a non-negative double combined into *mx_bits by an atomic maximum (mx_bits leads a block of
 // 16 bytes -- the refactorization's head -- which the caller zeroes first); tsrc: NULL, or the storage position of every entry

@@ -16,67 +16,7 @@
 
 #include "stmmqr_plan.h"
 #include "stmmqr_sparseqr.h"          // (stm_qr_tol_of_maxnorm)
-
-struct stmmqr_ls {
-    stm_long m = 0, n = 0, nrhs = 0, anz = 0;
-    double tol_arg = -2, tol = 0;                       // as given to create / as used by the last factorization
-    std::vector<stm_long> Ap, Bp, Bi, Q;                // A's column pointers; pattern and column order of [A B]
-    std::vector<double> Ax;                             // A's values as at create
-    stmmqr_analysis *sym = nullptr;
-    stmmqr_plan *plan = nullptr;
-    int device = -1;
-    DevBuf<double> d_val;                               // [Ax | B] on the device
-    DevBuf<double> d_resid;                             // residual norms of a solve with device pointers
-    std::vector<double> resid;                          // ... of the last solve, on the host (stmmqr_ls_resid)
-    bool ax_current = false;                            // d_val holds the values given at create (and tol belongs to them)
-    bool pattern_given = false;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    stmmqr_stats stats = {};
-    double sym_info[8] = {}, solve_ms = 0;
-    stm_long rank1 = 0, nanalyses = 0, nplans = 0, nsolves = 0;
-    // ---- the damped mode: m, anz, Ap, Bp, Bi above are those of [A; I] (m = rows of A + n, anz = entries of A + n), Ax holds A's own
-    // values as at create, and ax_current says that d_ax (not d_val, which every solve builds anew) holds them
-    bool damped = false;
-    stm_long am = 0, aanz = 0;                          // rows and entries of A
-    DevBuf<int> d_ap, d_ai;                             // A's column pointers and row indices, uploaded once at create
-    DevBuf<long long> d_ap2;                            // the column pointers of [A; I] for k_rf_colnorm (default tolerance only)
-    DevBuf<double> d_ax;                                // A's unweighted values: those of create, or a host array given to a solve
-    DevBuf<double> d_D;                                 // [n] the D_jj of the last solve, A's column order
-    DevBuf<double> d_head;                              // two doubles: where k_rf_colnorm leaves the largest column norm
-    DevBuf<double> d_w, d_x, d_dn;                      // for host arrays (made when first needed): w, X; |D x_j| of the last solve
-    hipEvent_t ev_build[2] = {nullptr, nullptr};
-    double build_ms = 0;
-    double damped_bytes() const
-    {
-        return 4.0 * (double)(d_ap.n + d_ai.n) + 8.0 * (double)(d_ap2.n + d_ax.n + d_D.n + d_head.n + d_w.n + d_x.n + d_dn.n);
-    }
-    // ---- the adjoint (stmmqr_ls_adjoint): made by the first call, grown on demand, never shrunk.  The plain object's int pattern of
-    // A goes into d_ap / d_ai above at its first call (the damped object has it from create).
-    bool last_solve_ok = false;                         // the factors and d_val belong to a solve that came to its end
-    struct Adjoint {
-        DevBuf<double> x, xb, z;                        // n x nrhs: the solution, its cotangent, (C'C)^-1 xbar
-        DevBuf<double> v, t;                            // (n + nrhs) x nrhs: what the product with [C | Bt] takes / what its transpose gives
-        DevBuf<double> rt, ut;                          // rows of C x nrhs: Bt - C x, C z
-        DevBuf<double> y, cz, res, dz, nrm;             // per batch: R' \ in R's row order, C z, the refinement's residual and step; norms
-        DevBuf<double> xT, zT, rtT, utT;                // the four k-fastest (nrhs > 1)
-        DevBuf<double> o_ax, o_bb, o_wb, o_db;          // outputs of a call with host arrays
-        bool have_z = false;                            // z belongs to a call that came to its end (stmmqr_ls_adjoint_z)
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        double bytes() const
-        {
-            return 8.0 * (double)(x.n + xb.n + z.n + v.n + t.n + rt.n + ut.n + y.n + cz.n + res.n + dz.n + nrm.n + xT.n + zT.n + rtT.n + utT.n +
-                                  o_ax.n + o_bb.n + o_wb.n + o_db.n);
-        }
-    } adj;
-    ~stmmqr_ls()
-    {
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-        for (auto &e : ev_build) if (e) (void)hipEventDestroy(e);
-        for (auto &e : adj.ev) if (e) (void)hipEventDestroy(e);
-        if (plan) stmmqr_plan_destroy(plan);
-        if (sym) stmmqr_analysis_free(sym);
-    }
-};
+#include "stmmqr_lsobj.h"             // (struct stmmqr_ls)
 
 extern "C" {
 
@@ -452,15 +392,7 @@ static int ls_adjoint_impl(stmmqr_ls *ls, const double *X, stm_long ldx, const d
     HIPCHK(hipEventRecord(A.ev[0], st));
     HIPCHK(hipMemsetAsync(K.d_err.p, 0, sizeof(int), st));
     PASS(ensure_rt(P, RT_SPLIT));
-    if (!L.d_ap.p) {                                        // the plain object's int pattern of A, once
-        std::vector<int> ap((size_t)n + 1), ai((size_t)std::max<stm_long>(aanz, 1), 0);
-        for (stm_long j = 0; j <= n; j++) ap[(size_t)j] = (int)L.Ap[(size_t)j];
-        for (stm_long p = 0; p < aanz; p++) ai[(size_t)p] = (int)L.Bi[(size_t)p];
-        LCHK(L.d_ap.alloc(ap.size()));
-        LCHK(L.d_ai.alloc(ai.size()));
-        HIPCHK(hipMemcpy(L.d_ap.p, ap.data(), ap.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(L.d_ai.p, ai.data(), ai.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
+    PASS(ls_ensure_int_pattern(L));                         // the plain object's int pattern of A, once
     const double *dw = w;
     if (w && !on_device) {
         if (!L.d_w.p) LCHK(L.d_w.alloc((size_t)std::max<stm_long>(am, 1)));
@@ -619,7 +551,7 @@ int stmmqr_ls_info(const stmmqr_ls *ls, double *info)
     if (!ls || !info) return stm_fail(STMMQR_ERR_INVALID, "stmmqr_ls_info: null argument");
     const stm_qr_symbolic *S = stmmqr_analysis_symbolic(ls->sym);
     info[0] = (double)ls->rank1; info[1] = (double)S->nf; info[2] = ls->stats.flops; info[3] = ls->sym_info[0];
-    info[4] = ls->stats.ms_total; info[5] = ls->solve_ms; info[6] = ls->stats.device_bytes + (double)ls->d_val.n * sizeof(double) + ls->damped_bytes() + ls->adj.bytes();
+    info[4] = ls->stats.ms_total; info[5] = ls->solve_ms; info[6] = ls->stats.device_bytes + (double)ls->d_val.n * sizeof(double) + ls->damped_bytes() + ls->adj.bytes() + ls->rob.bytes();
     info[7] = (double)ls->stats.retries; info[8] = (double)ls->stats.reschedules;
     info[9] = (double)ls->nanalyses; info[10] = (double)ls->nplans; info[11] = (double)ls->nsolves;
     info[12] = ls->tol; info[13] = (double)ls->nrhs;
